@@ -9,8 +9,14 @@ One "step" = the reference's training step (scripts/train_gat_pyg.py:312-323):
 value = E * L * K / t over K timed steps (E = edge_index columns, L = 2 layers).
 Inputs (graph, features, triples) are resident in HBM before the timed region.
 
-Usage: python bench.py [--gpus N --steps K --warmup W]
+Usage: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
 N>1: launched by torch.distributed.run, one rank per GPU.
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value,
+ms_per_step, the workload's description, the loss).  --dump-outputs DIR also writes what the last
+timed step computed (dump_outputs below).  --full adds everything that takes runs of its own after
+the timed region: the per-kernel breakdown, the roofline of the dominant kernel with the
+streaming-copy yardstick, and the CPU oracle baseline.
 """
 from __future__ import annotations
 
@@ -52,8 +58,16 @@ def parse():
     ap.add_argument("--scale", type=float, default=None,
                     help="config 5 size multiplier (default world/8: one GPU's share of the 8-GPU run, "
                          "so the per-GPU work is the same at every N)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the per-kernel breakdown (an eager replay of the "
+                         "step under HIP events), the dominant kernel's roofline with the streaming-copy "
+                         "yardstick, and the CPU oracle baseline; off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, embeddings Z, updated parameters and "
+                         "their gradients) as DIR/<name>.npy, float32; arrays over 8 MiB as a fixed seeded "
+                         "sample of their rows")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=15.0,
-                    help="approximate CPU time budget of the oracle baseline leg (0 disables)")
+                    help="with --full: approximate CPU time budget of the oracle baseline leg (0 disables)")
     ap.add_argument("--traffic-json", default=None,
                     help="committed PMC summary (default: profiles/r06/cfg2_pmc_traffic.json for config 2, "
                          "profiles/r03/cfg5_pmc_traffic.json for config 5 at its default scale)")
@@ -207,6 +221,37 @@ def cpu_baseline(g: data.UIGraph, feats: np.ndarray, hidden: int, layers: int, b
                       f"torch {torch.__version__} CPU"}
 
 
+DUMP_ARRAY_BYTES = 8 << 20    # larger arrays are written as a row sample of at most this size
+DUMP_TOTAL_BYTES = 64 * 10**6
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> dict:
+    """--dump-outputs: each named device tensor as out_dir/<name>.npy (float32).  An array over
+    DUMP_ARRAY_BYTES is written as a sample of its rows, drawn without replacement by a generator
+    seeded with 0 from the row count alone (sorted), so two builds given the same arguments write
+    the same rows.  Returns name -> [rows written, rows of the array]."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    total, written = 0, {}
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.reshape(1) if t.dim() == 0 else t
+        rows = t.size(0)
+        row_bytes = 4 * max(t.numel() // max(rows, 1), 1)
+        keep = rows
+        if rows * row_bytes > DUMP_ARRAY_BYTES:
+            keep = max(1, DUMP_ARRAY_BYTES // row_bytes)
+            idx = np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))
+            t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+        a = t.to(torch.float32).cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_TOTAL_BYTES:
+            raise RuntimeError(f"--dump-outputs: more than {DUMP_TOTAL_BYTES} bytes at {name}")
+        np.save(out / f"{name}.npy", a)
+        written[name] = [keep, rows]
+    return written
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -287,6 +332,7 @@ def main():
     # faster inside the captured step (1.890 vs 1.881 ms, profiles/r05/w1_bench.log)
     bpr_overlap = os.environ.get("PPGAT_BPR_OVERLAP", "0") == "1"
     one = torch.ones((), dtype=torch.float32, device=dev)  # loss.backward()'s seed, made once (no fill per step)
+    kept = {}  # --dump-outputs: the last step's embeddings (inside a captured step: the replays' buffer)
 
     def step():
         model.train()
@@ -306,6 +352,8 @@ def main():
             opt.zero_grad(set_to_none=True)
             loss.backward(one)
         opt.step()
+        if args.dump_outputs:
+            kept["Z"] = Z.detach()
         return loss
 
     graph = None
@@ -360,7 +408,8 @@ def main():
     torch.cuda.synchronize()
     note("warm; timing")
     _lib.profile_reset()
-    _lib.profile_enable(graph is None)  # per-kernel events in eager mode only (not capturable)
+    # --full: per-kernel events inside the timed region in eager mode only (not capturable)
+    _lib.profile_enable(args.full and graph is None)
     if dist_path:
         torch.distributed.barrier()
     torch.cuda.synchronize()
@@ -376,19 +425,8 @@ def main():
         torch.distributed.barrier()
     el = time.perf_counter() - t0
     _lib.profile_enable(False)
-    kern_src = "HIP events on the launch stream inside the timed region"
     if graph is not None:
         loss = loss_static
-        # graph replays carry no per-kernel events: time the same step eagerly for the
-        # kernel breakdown and the roofline (after the timed region; not part of value)
-        torch.cuda.synchronize()
-        _lib.profile_reset()
-        _lib.profile_enable(True)
-        for _ in range(args.steps):
-            step()
-        torch.cuda.synchronize()
-        _lib.profile_enable(False)
-        kern_src = "HIP events, eager replay of the same step after the timed graph replays"
     if dist_path:
         tt = torch.tensor([el], dtype=torch.float64)
         tt = tt.to(dev) if args.dist_backend == "nccl" else tt
@@ -397,63 +435,107 @@ def main():
     loss_val = loss.detach().clone()
     if dist_path:  # each rank's loss covers its own users' triples: the job's loss is their sum
         comm.all_reduce_(loss_val)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what a caller of the step holds after the last timed step (before --full steps again):
+        # the loss, the embeddings, and the parameters with the gradients Adam just applied
+        arrays = {"loss": loss, "Z": kept["Z"]}
+        for name, p in model.named_parameters():
+            arrays[f"param.{name}"] = p
+            if p.grad is not None:
+                arrays[f"grad.{name}"] = p.grad
+        dumped = dump_outputs(args.dump_outputs, arrays)
     K = args.steps
     H, C = args.heads, args.hidden
     # the multi-head layers run aggregate-then-transform when H*C exceeds the input width
     xform_k = C if (H > 1 and H * C > C and pkg.hip_ops.xgat_supported(C, H, C)) else 0
-    # the backward formulation hip_ops.xgat_backward picks for these layer sizes
-    src_homed = dist_path and part == "halo" and xform_k and pkg.dist.source_homed_backward(dg)
-    if src_homed:  # the source-homed backward (dist._halo_xgat_backward): deferred D unless PPGAT_XGAT_GATHER=g
-        gather_mode = "g" if os.environ.get("PPGAT_XGAT_GATHER") == "g" else "gd"
-    elif xform_k and dist_path and part == "halo":  # the formulation the local layer sizes select
-        gather_mode = pkg.hip_ops._xgat_gather_mode(C, H, dg.R, dg.n_own, dg.bwd_view.n_bwd_edges, C)
-    else:
-        gather_mode = pkg.hip_ops._xgat_gather_mode(C, H) if xform_k else None
-    gather_g = gather_mode in ("g", "gd")
-    kern = {k: _lib.profile_read(k) for k in ("scores", "fwd", "bwd_pro", "bwd_src", "bwd_epi", "bwd_red",
-                                               "proj", "proj_bwd", "gemm_tn", "adam")}
-    fused_ms = sum(ms for k, (ms, _) in kern.items() if k not in ("proj", "proj_bwd", "gemm_tn", "adam"))
     value = E * args.layers * K / el  # the whole job: every edge of the global graph, once per layer
-    dom = max(("fwd", "bwd_src", "bwd_epi"), key=lambda k: kern[k][0])
-    dom_ms, dom_n = kern[dom]
-    # one layer pass may be several launches (the sharded backward runs halo / item sources
-    # first and the rest after the exchange): average per layer pass, K steps x L layers
-    passes = args.steps * args.layers
-    avg_s = dom_ms / max(passes, 1) / 1e3
-    if dist_path:
-        # rank 0's kernels run over its local graph: price them on its own rows and edges
-        if part == "replicated":
-            v = dg.view
+
+    def full_figures():
+        """--full: the per-kernel breakdown, the dominant kernel's roofline and the copy yardstick."""
+        kern_src = "HIP events on the launch stream inside the timed region"
+        if graph is not None:
+            # graph replays carry no per-kernel events: time the same step eagerly for the
+            # kernel breakdown and the roofline (after the timed region; not part of value)
+            torch.cuda.synchronize()
+            _lib.profile_reset()
+            _lib.profile_enable(True)
+            for _ in range(args.steps):
+                step()
+            torch.cuda.synchronize()
+            _lib.profile_enable(False)
+            kern_src = "HIP events, eager replay of the same step after the timed graph replays"
+        # the backward formulation hip_ops.xgat_backward picks for these layer sizes
+        src_homed = dist_path and part == "halo" and xform_k and pkg.dist.source_homed_backward(dg)
+        if src_homed:  # the source-homed backward (dist._halo_xgat_backward): deferred D unless PPGAT_XGAT_GATHER=g
+            gather_mode = "g" if os.environ.get("PPGAT_XGAT_GATHER") == "g" else "gd"
+        elif xform_k and dist_path and part == "halo":  # the formulation the local layer sizes select
+            gather_mode = pkg.hip_ops._xgat_gather_mode(C, H, dg.R, dg.n_own, dg.bwd_view.n_bwd_edges, C)
         else:
-            v = dg.fwd_view if dom == "fwd" else dg.bwd_view
-        if src_homed and dom != "fwd":  # the backward passes run over the own sources' out-edges
-            ab = algo_bytes(dom, dg.n_own, dg.src_views.n_edges, H, C, args.attn_dropout > 0, xform_k,
-                            dz_slot=False, gather_g=gather_mode)
-        else:
-            ab = algo_bytes(dom, v.n_rows, v.n_fwd_edges if dom == "fwd" else v.n_bwd_edges, H, C,
-                            args.attn_dropout > 0, xform_k, dz_slot=part != "replicated",
-                            gather_g=gather_mode if gather_g else False)
-    else:
-        ab = algo_bytes(dom, N, E, H, C, args.attn_dropout > 0, xform_k, gather_g=gather_mode if gather_g else False)
-    achieved = ab / avg_s / 1e9
-    traffic = traffic_src = traffic_dram = None
-    try:
+            gather_mode = pkg.hip_ops._xgat_gather_mode(C, H) if xform_k else None
+        gather_g = gather_mode in ("g", "gd")
+        kern = {k: _lib.profile_read(k) for k in ("scores", "fwd", "bwd_pro", "bwd_src", "bwd_epi", "bwd_red",
+                                                   "proj", "proj_bwd", "gemm_tn", "adam")}
+        fused_ms = sum(ms for k, (ms, _) in kern.items() if k not in ("proj", "proj_bwd", "gemm_tn", "adam"))
+        dom = max(("fwd", "bwd_src", "bwd_epi"), key=lambda k: kern[k][0])
+        dom_ms, dom_n = kern[dom]
+        # one layer pass may be several launches (the sharded backward runs halo / item sources
+        # first and the rest after the exchange): average per layer pass, K steps x L layers
+        passes = args.steps * args.layers
+        avg_s = dom_ms / max(passes, 1) / 1e3
         if dist_path:
-            raise LookupError("the committed PMC summary is for the unsharded graph")
-        tj_path = args.traffic_json or str(ROOT / "profiles" / ("r03/cfg5_pmc_traffic.json" if args.config == 5
-                                                                 else "r06/cfg2_pmc_traffic.json"))
-        tj_ = json.loads(Path(tj_path).read_text())
-        # PMC summaries are per workload (config, scale) and per multi-head backward formulation
-        if tj_.get("config", 2) == args.config and tj_.get("scale", scale if args.config == 5 else None) == (
-                scale if args.config == 5 else None) and (
-                not xform_k or tj_.get("bwd_gather", "gt") == (gather_mode if gather_g else "gt")):
-            traffic = tj_.get("per_launch_bytes", {}).get(dom)
-            traffic_src = os.path.relpath(tj_path, ROOT)
-            traffic_dram = tj_.get("per_launch_dram_bytes", {}).get(dom)
-    except Exception:
-        pass
-    copies = measured_copy_gbs(dev) if rank == 0 else None
-    copy_gbs = copies["f4"] if copies else None
+            # rank 0's kernels run over its local graph: price them on its own rows and edges
+            if part == "replicated":
+                v = dg.view
+            else:
+                v = dg.fwd_view if dom == "fwd" else dg.bwd_view
+            if src_homed and dom != "fwd":  # the backward passes run over the own sources' out-edges
+                ab = algo_bytes(dom, dg.n_own, dg.src_views.n_edges, H, C, args.attn_dropout > 0, xform_k,
+                                dz_slot=False, gather_g=gather_mode)
+            else:
+                ab = algo_bytes(dom, v.n_rows, v.n_fwd_edges if dom == "fwd" else v.n_bwd_edges, H, C,
+                                args.attn_dropout > 0, xform_k, dz_slot=part != "replicated",
+                                gather_g=gather_mode if gather_g else False)
+        else:
+            ab = algo_bytes(dom, N, E, H, C, args.attn_dropout > 0, xform_k,
+                            gather_g=gather_mode if gather_g else False)
+        achieved = ab / avg_s / 1e9
+        traffic = traffic_src = traffic_dram = None
+        try:
+            if dist_path:
+                raise LookupError("the committed PMC summary is for the unsharded graph")
+            tj_path = args.traffic_json or str(ROOT / "profiles" / ("r03/cfg5_pmc_traffic.json" if args.config == 5
+                                                                     else "r06/cfg2_pmc_traffic.json"))
+            tj_ = json.loads(Path(tj_path).read_text())
+            # PMC summaries are per workload (config, scale) and per multi-head backward formulation
+            if tj_.get("config", 2) == args.config and tj_.get("scale", scale if args.config == 5 else None) == (
+                    scale if args.config == 5 else None) and (
+                    not xform_k or tj_.get("bwd_gather", "gt") == (gather_mode if gather_g else "gt")):
+                traffic = tj_.get("per_launch_bytes", {}).get(dom)
+                traffic_src = os.path.relpath(tj_path, ROOT)
+                traffic_dram = tj_.get("per_launch_dram_bytes", {}).get(dom)
+        except Exception:
+            pass
+        copies = measured_copy_gbs(dev) if rank == 0 else None
+        copy_gbs = copies["f4"] if copies else None
+        return {
+            "kernel_timing": kern_src,
+            "fused_kernel_edges_per_sec": E * args.layers * K / (fused_ms / 1e3) if fused_ms else None,
+            "kernel_ms_per_step": {k: ms / K for k, (ms, n) in kern.items()},
+            "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                         "traffic_source": traffic_src,
+                         # the L2's fabric requests destined for DRAM (TCC_EA0_*REQ_DRAM / *REQ): the
+                         # memory-side Infinity Cache sits behind them, so its hits are not split off
+                         "traffic_dram_destined": traffic_dram,
+                         "algo_bytes_per_launch": ab, "avg_launch_ms": avg_s * 1e3, "launches": dom_n,
+                         "launches_per_layer_pass": dom_n / max(passes, 1),
+                         "measured_copy_gbs": copy_gbs,
+                         "frac_of_copy": achieved / copy_gbs if copy_gbs else None,
+                         "torch_copy_gbs": copies["torch"] if copies else None},
+        }
+
+    full = full_figures() if args.full else {}
     if args.config == 5:
         metric = "edges/sec GAT fwd+bwd, d=256 heads=4, 200M-edge synthetic (config 5)"
         workload = (f"cfg5 x{scale:g}: PyGGAT train step (fwd+BPR+bwd+Adam), {g.n_users:,} users + {g.n_items:,} "
@@ -501,24 +583,13 @@ def main():
                  "fp32 operands and results on the matrix cores through the bf16 three-term split (6 MFMAs "
                  "per product, <= 2^-24 relative per product: k_projx, k_dxw; DESIGN.md 4.3), fp32 MFMA "
                  "for the small weight-gradient products"),
-        "kernel_timing": kern_src,
-        "fused_kernel_edges_per_sec": E * args.layers * K / (fused_ms / 1e3) if fused_ms else None,
-        "kernel_ms_per_step": {k: ms / K for k, (ms, n) in kern.items()},
-        "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                     "traffic_source": traffic_src,
-                     # the L2's fabric requests destined for DRAM (TCC_EA0_*REQ_DRAM / *REQ): the
-                     # memory-side Infinity Cache sits behind them, so its hits are not split off
-                     "traffic_dram_destined": traffic_dram,
-                     "algo_bytes_per_launch": ab, "avg_launch_ms": avg_s * 1e3, "launches": dom_n,
-                     "launches_per_layer_pass": dom_n / max(passes, 1),
-                     "measured_copy_gbs": copy_gbs,
-                     "frac_of_copy": achieved / copy_gbs if copy_gbs else None,
-                     "torch_copy_gbs": copies["torch"] if copies else None},
+        **full,  # --full: kernel_timing, fused_kernel_edges_per_sec, kernel_ms_per_step, roofline
         "loss": float(loss_val.item()),
         "optimizer": "Adam (libppgat device kernel, torch.optim.Adam semantics)",
     }
-    if rank == 0 and world == 1 and args.cpu_baseline_seconds > 0 and args.config != 5:
+    if dumped is not None:
+        result["dumped_outputs"] = {"dir": args.dump_outputs, "rows_written_of": dumped}
+    if args.full and rank == 0 and world == 1 and args.cpu_baseline_seconds > 0 and args.config != 5:
         result["cpu_baseline"] = cpu_baseline(g, feats_np, C, args.layers, args.cpu_baseline_seconds)
     if rank == 0:
         print(json.dumps(result), flush=True)

@@ -54,7 +54,7 @@ for s in $STEPS; do
             done ;;
     e4lab) run gemm5_base 300 python tools/bench_gemm.py --cfg5 --iters 10 && \
            run gemm5_e4 300 env PPGAT_LIB=lab_build/libppgat.so PPGAT_NNH_E4=1 python tools/bench_gemm.py --cfg5 --iters 10 && \
-           run bench5_e4 600 env PPGAT_LIB=lab_build/libppgat.so PPGAT_NNH_E4=1 python -u bench.py --config 5 --steps 10 --warmup 3 ;;
+           run bench5_e4 600 env PPGAT_LIB=lab_build/libppgat.so PPGAT_NNH_E4=1 python -u bench.py --full --config 5 --steps 10 --warmup 3 ;;
     occ2lab) run gemm5_base 300 python tools/bench_gemm.py --cfg5 --iters 10 && \
            run gemm5_occ2 300 env PPGAT_LIB=lab_build/libppgat.so PPGAT_NNH_OCC2=1 python tools/bench_gemm.py --cfg5 --iters 10 ;;
     tnpmc) run tn5_256 120 python tools/bench_gemm.py --tn5 --iters 10 && \
@@ -69,13 +69,13 @@ for s in $STEPS; do
     profprobe640) (cd /tmp && run rocprof_probe5_640 900 rocprofv3 --kernel-trace --stats -d "$OUT/profprobe640" -o run --output-format csv -- python "$R/tools/scale_probe.py" --config 5 --world 8 --rank ${PROBE_RANK:-0} --streams --a2a-gbs 640 --steps 3 --warmup 1) ;;
     profprobe) (cd /tmp && run rocprof_probe5 900 rocprofv3 --kernel-trace --stats -d "$OUT/profprobe" -o run --output-format csv -- python "$R/tools/scale_probe.py" --config 5 --world 8 --rank ${PROBE_RANK:-7} --streams --steps 3 --warmup 1) ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 600 python bench.py $BENCH_ARGS ;;
-    bench3) run bench_cfg3 600 python bench.py --config 3 --cpu-baseline-seconds 0 ;;
+    bench) run bench 600 python bench.py --full $BENCH_ARGS ;;
+    bench3) run bench_cfg3 600 python bench.py --full --config 3 --cpu-baseline-seconds 0 ;;
     copylab) run copy_lab 120 tools/copy_lab ;;
-    fwdxu) for u in ${FWDXU:-8 6 4}; do run "bench5_fwdx_u$u" 600 env PPGAT_LIB=lab_build/libppgat.so PPGAT_FWDX_U=$u python -u bench.py --config 5 --steps 5 --warmup 2 --graph off; done ;;
-    bench5full) run bench_cfg5_full 1000 python -u bench.py --config 5 --scale 1 --steps ${FULL_STEPS:-3} --warmup 1 --graph ${FULL_GRAPH:-on} ;;
+    fwdxu) for u in ${FWDXU:-8 6 4}; do run "bench5_fwdx_u$u" 600 env PPGAT_LIB=lab_build/libppgat.so PPGAT_FWDX_U=$u python -u bench.py --full --config 5 --steps 5 --warmup 2 --graph off; done ;;
+    bench5full) run bench_cfg5_full 1000 python -u bench.py --full --config 5 --scale 1 --steps ${FULL_STEPS:-3} --warmup 1 --graph ${FULL_GRAPH:-on} ;;
     prof5full) (cd /tmp && run rocprof_cfg5_full 1000 rocprofv3 --kernel-trace --stats -d "$OUT/prof5full" -o run --output-format csv -- python -u "$R/bench.py" --config 5 --scale 1 --steps 2 --warmup 1 --graph off) ;;
-    bench5) run bench_cfg5 900 python -u bench.py --config 5 --steps 10 --warmup 3 ;;
+    bench5) run bench_cfg5 900 python -u bench.py --full --config 5 --steps 10 --warmup 3 ;;
     prof5)  (cd /tmp && run rocprof_cfg5 900 rocprofv3 --kernel-trace --stats -d "$OUT/prof5" -o run --output-format csv -- python "$R/bench.py" --config 5 --steps 5 --warmup 2) ;;
     pmc5)  (cd /tmp && run pmc5_fetch 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/pmc5_fetch" -o fetch -- python "$R/bench.py" --config 5 --steps 2 --warmup 1 --graph off --cpu-baseline-seconds 0) && \
            (cd /tmp && run pmc5_write 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$OUT/pmc5_write" -o write -- python "$R/bench.py" --config 5 --steps 2 --warmup 1 --graph off --cpu-baseline-seconds 0) && \
