@@ -195,11 +195,9 @@ hipError_t gemm_nn(const float* X, int64_t ldx, int64_t M, int K, const float* B
                    void* ws = nullptr, const float* rS = nullptr, int64_t ldrs = 0, int nv = 0,
                    const float* rA = nullptr, int64_t ldra = 0);
 size_t gemm_nn_workspace_bytes(int64_t M, int K, int N);
-// the split bf16 images of a GEMM's B operand per (32 nt columns, 32-deep k chunk), once per call
-hipError_t nnx_presplit(const float* B, int64_t ldb, int bmode, int K, int N, int nt, uint16_t* img, hipStream_t st);
+// bytes of the split bf16 images of a GEMM's B operand per (32 nt columns, 32-deep k chunk)
 size_t nnx_image_bytes(int K, int N, int nt);
-// the fp16 two-term family (PPGAT_GEMM_F16=0 turns it off): pre-split images + column exponents
-bool gemm_f16_enabled();
+// the fp16 two-term family: pre-split images + column exponents
 size_t nnh_image_bytes(int K, int N, int nt);
 hipError_t nnh_presplit(const float* B, int64_t ldb, int bmode, int K, int N, int nt, uint16_t* img, int* ecol,
                         hipStream_t st);
@@ -239,7 +237,6 @@ hipError_t xgat_bwd_edges_g(const ItemsArg& it, const int32_t* row, const int32_
                             float* S, int64_t lds, float* dz, float* partial, const int32_t* hub_row,
                             const int32_t* hub_ptr, int64_t n_hubs, hipStream_t st, float* pz = nullptr,
                             unsigned* gmax = nullptr);
-int nnh_pipeline_variant();  // the fp16 NN main loop: 1 k_gemm_nnh, 2 k_gemm_nnh2, 3 k_gemm_nnh3 (PPGAT_NNH2)
 hipError_t xgat_nstate_set_d(float* nstate, const float* D, int64_t n, int H, hipStream_t st);
 hipError_t xgat_nstate(const float* s_dst, const float* m, const float* invl, const float* D, int64_t n, int H,
                        float* nstate, hipStream_t st);

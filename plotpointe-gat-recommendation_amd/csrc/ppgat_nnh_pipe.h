@@ -11,7 +11,8 @@
 //    during chunk c - 1, and the second half of those steps carries chunk c + 1's preparation in
 //    its gaps: row maxima, the online row scale (split::row_scale_plan), the fp16 split -- the
 //    independent VALU work issues while the wave's MFMAs run, so no chunk starts with the MFMA
-//    pipe idle behind ~100 VALU instructions (k_gemm_nnh2 did that at the top of every chunk);
+//    pipe idle behind ~100 VALU instructions (its predecessor k_gemm_nnh2, now a lab-build
+//    kernel, did that at the top of every chunk);
 //  * after the products: the rare accumulator rescale (split::row_rescale), then an explicit
 //    vmcnt wait for this wave's DMA of chunk c + 1 and a bare s_barrier.
 // The products and their order are k_gemm_nnh's (bitwise equal results).
@@ -54,25 +55,17 @@ __device__ __forceinline__ void wait_vm() {
 // column block's chunk images (chunks x NnhImg<NT>::ELEMS); sB: LDS, 3 x ELEMS; sFw: this wave's
 // 32-float LDS scratch; loadx(c, x): this lane's 16 values of chunk c (4 float4, the fragment
 // order of split2h: x[g] = row[32 c + 8 g + 4 hf .. + 3]).
-// BD: B fragments read BD MFMA steps ahead (1: the step before, as k_gemm_nnh2; 2: two steps,
-// eight more VGPRs, for LDS latency under eight waves of reads).  PRIO: waves 4-7 (the second-
-// dispatched half, the issue-arbitration loser) at s_setprio 1 for the whole loop.
-// LAB (diagnostics only, instantiated in lab builds -DPPGAT_LAB_BUILD=1, never in libppgat.so;
-// PPGAT_NNH2_LAB with PPGAT_NNH2=3; results wrong), bits: 1 = no X loads
-// after the first two chunks, 2 = no B DMA after the first two chunks, 16 = no B fragment reads
-// inside a chunk's MFMA steps (the first BD per chunk only), 32 = no preparation of the next
-// chunk (its fragments reused)
-// XT: loadx(c, x) delivers the chunk COALESCED -- lane l holds floats [4 (l & 7), +4) of rows
+// B fragments are read one MFMA step ahead.
+// XT (instantiated in lab builds only): loadx(c, x) delivers the chunk COALESCED -- lane l holds floats [4 (l & 7), +4) of rows
 // (l >> 3) + 8 j, j = 0..3 (each load instruction reads 8 whole 128-B row segments, not 32-B
 // pieces of 32 rows) -- and the preparation turns it into the fragment layout through this
 // wave's LDS scratch sXw [32 rows][36 floats] (4 ds_write_b128 + 4 ds_read_b128 per chunk,
 // conflict-free with the 36-float row stride).  The same values in the same fragment slots: the
 // products are bitwise those of the direct layout.
-template <int NT, int BD = 1, bool PRIO = false, int LAB = 0, bool XT = false, class LoadX>
+template <int NT, bool XT = false, class LoadX>
 __device__ __forceinline__ void nnh3_loop(const uint16_t* img, uint16_t* sB, int chunks, const LoadX& loadx,
                                           split::f32x16 (&acc)[NT], int& erow, float* sFw, int wv, int lane,
                                           float* sXw = nullptr) {
-  static_assert(BD == 1 || BD == 2, "B read depth");
   using I = NnhImg<NT>;
   constexpr int LDK = I::LDK, PART = I::PART, NI = I::BYTES / 1024;
   constexpr int STEPS = (I::KC / 16) * NT;  // MFMA steps (three products each) per chunk
@@ -153,7 +146,6 @@ __device__ __forceinline__ void nnh3_loop(const uint16_t* img, uint16_t* sB, int
     erow = pen;
     set = set || pneed;
   };
-  if (PRIO && wv >= 4) __builtin_amdgcn_s_setprio(1);
   float4 xA[4], xB[4];
   split::u32x4 fxA[2][2], fxB[2][2];
   issue(0);
@@ -171,29 +163,28 @@ __device__ __forceinline__ void nnh3_loop(const uint16_t* img, uint16_t* sB, int
                   split::u32x4 (&fxn)[2][2], auto has_next) {
     constexpr bool NEXT = decltype(has_next)::value;
     const bool ahead = c + 2 < chunks;
-    if (ahead && !(LAB & 2)) issue(c + 2);
-    if (!(LAB & 1)) loadx(ahead ? c + 2 : chunks - 1, xl);  // the last two chunks re-read chunk chunks - 1
+    if (ahead) issue(c + 2);
+    loadx(ahead ? c + 2 : chunks - 1, xl);  // the last two chunks re-read chunk chunks - 1
     const uint16_t* sb = sB + (c % 3) * I::ELEMS;
     auto read_b = [&](int i, split::u32x4 (&f)[2]) {
       const int off = (32 * (i % NT) + r) * LDK + 16 * (i / NT) + 8 * hf;
 #pragma unroll
       for (int p = 0; p < 2; ++p) f[p] = *reinterpret_cast<const split::u32x4*>(&sb[p * PART + off]);
     };
-    split::u32x4 fb[BD + 1][2];
-#pragma unroll
-    for (int i = 0; i < BD; ++i) read_b(i, fb[i]);
+    split::u32x4 fb[2][2];
+    read_b(0, fb[0]);
 #pragma unroll
     for (int i = 0; i < STEPS; ++i) {
       const int u = i / NT, t = i % NT;
-      if (!(LAB & 16) && i + BD < STEPS) read_b(i + BD, fb[(i + BD) % (BD + 1)]);
-      acc[t] = split::mfma32_h3(fxc[u], fb[(LAB & 16) ? 0 : i % (BD + 1)], acc[t]);
-      if constexpr (NEXT && !(LAB & 32)) {
+      if (i + 1 < STEPS) read_b(i + 1, fb[(i + 1) & 1]);
+      acc[t] = split::mfma32_h3(fxc[u], fb[i & 1], acc[t]);
+      if constexpr (NEXT) {
         if (i >= STEPS / 2) {
 #pragma unroll
           for (int k = 0; k < PPS; ++k) prep((i - STEPS / 2) * PPS + k, xn, fxn);
         }
       }
-      if (i + BD < STEPS) __builtin_amdgcn_sched_group_barrier(0x0100, 2, 0);
+      if (i + 1 < STEPS) __builtin_amdgcn_sched_group_barrier(0x0100, 2, 0);
       __builtin_amdgcn_sched_group_barrier(0x0008, 1, 0);
       __builtin_amdgcn_sched_group_barrier(0x0002, 6, 0);
       __builtin_amdgcn_sched_group_barrier(0x0008, 1, 0);
@@ -201,12 +192,10 @@ __device__ __forceinline__ void nnh3_loop(const uint16_t* img, uint16_t* sB, int
       __builtin_amdgcn_sched_group_barrier(0x0008, 1, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
-    if constexpr (NEXT && !(LAB & 32)) commit();
+    if constexpr (NEXT) commit();
     // DMA(c + 1) has landed (issued after it: X(c + 1), DMA(c + 2) if any, X(c + 2)) and every
     // wave is done with buffer c % 3 before DMA(c + 3) (issued in chunk c + 1) overwrites it
-    if (LAB) {
-      wait_vm<0>();
-    } else if (ahead) {
+    if (ahead) {
       if (full) wait_vm<4 + ND + 4>(); else wait_vm<4 + ND - 1 + 4>();
     } else {
       wait_vm<4 + 4>();
@@ -221,7 +210,6 @@ __device__ __forceinline__ void nnh3_loop(const uint16_t* img, uint16_t* sB, int
   }
   body(chunks - 2, xA, xB, fxA, fxB, yes{});
   body(chunks - 1, xB, xA, fxB, fxA, no{});
-  if (PRIO && wv >= 4) __builtin_amdgcn_s_setprio(0);
 }
 
 }  // namespace ppgat

@@ -416,152 +416,23 @@ __global__ void __launch_bounds__(256, 2) k_gemm_nnx(NnArg a) {
 }
 
 // ---------------------------------------------------------------------------
-// NN GEMM on the split bf16 matrix cores, B pre-split once per call (the large-M shapes:
-// config 5's [1.9M x 1024] x [1024 x 256] and [1.9M x 256] x [256 x 1024]).
-//
-// k_gemm_nnx splits its 32-deep B chunk while staging it (per workgroup, per chunk: ~1.8 VALU
-// instructions per MFMA, PMC profiles/r03/v1_gemm_nnx_cfg5_pmc.json: MFMA busy 0.49) and
-// stages it through registers with two barriers per chunk.  Here:
-//  * k_nnx_presplit writes the three bf16 images of every (column block, k chunk) to the
-//    workspace ONCE per call, in exactly the LDS layout k_gemm_nnx uses (80-B rows, the
-//    permuted reduction order), so the products are the same -- bitwise equal results;
-//  * k_gemm_nnp stages them with global_load_lds_dwordx4 (an image is a contiguous byte
-//    range, so the lane-linear LDS destination is the image itself), two LDS buffers, one
-//    barrier per chunk, 8 waves (256 rows) sharing every staged chunk.
+// The pre-split NN kernels: 8 waves x 32 rows per workgroup share every staged B chunk.
 // ---------------------------------------------------------------------------
-constexpr int kPBM = 256;  // rows per k_gemm_nnp workgroup (8 waves x 32)
+constexpr int kPBM = 256;  // rows per workgroup (8 waves x 32)
 
+// the three-part bf16 chunk image of the lab build's k_gemm_nnp (lab/ppgat_xform_lab.h); here for
+// nnx_image_bytes, which sizes the workspaces of both builds alike
 template <int NT>
 struct NnpImg {
   static constexpr int KC = 32, BN = 32 * NT, LDK = KC + 8, PART = BN * LDK, ELEMS = 3 * PART, BYTES = 2 * ELEMS;
   static_assert(BYTES % 1024 == 0, "an image is a whole number of 1-KB wave copies");
 };
 
-template <int NT, int BMODE>
-__global__ void __launch_bounds__(256) k_nnx_presplit(const float* __restrict__ B, int64_t ldb, int K, int N,
-                                                      uint16_t* __restrict__ img) {
-  using I = NnpImg<NT>;
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= (int64_t)N * (K / 4)) return;
-  const int ng = (int)(t % N), kq = (int)(t / N);
-  const int k0 = 4 * kq, c = k0 / I::KC, q = (k0 % I::KC) / 4;
-  const int nb = ng / I::BN, n = ng % I::BN;
-  float v[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) v[j] = BMODE == 0 ? B[(int64_t)(k0 + j) * ldb + ng] : B[(int64_t)ng * ldb + k0 + j];
-  uint2 h, mm, l;
-  uint32_t* ph = &h.x;
-  uint32_t* pm = &mm.x;
-  uint32_t* pl = &l.x;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const uint32_t hh = split::pk_bf16(v[2 * i], v[2 * i + 1]);
-    const float r0 = v[2 * i] - split::bf_lo(hh), r1 = v[2 * i + 1] - split::bf_hi(hh);
-    const uint32_t m2 = split::pk_bf16(r0, r1);
-    ph[i] = hh;
-    pm[i] = m2;
-    pl[i] = split::pk_bf16(r0 - split::bf_lo(m2), r1 - split::bf_hi(m2));
-  }
-  const int kk = 16 * (q >> 2) + 8 * (q & 1) + 4 * ((q >> 1) & 1);
-  uint16_t* base = img + ((int64_t)nb * (K / I::KC) + c) * I::ELEMS + n * I::LDK + kk;
-  *reinterpret_cast<uint2*>(base) = h;
-  *reinterpret_cast<uint2*>(base + I::PART) = mm;
-  *reinterpret_cast<uint2*>(base + 2 * I::PART) = l;
-}
-
-template <int NT>
-__global__ void __launch_bounds__(512, 1) k_gemm_nnp(NnArg a, const uint16_t* __restrict__ img) {
-  using I = NnpImg<NT>;
-  constexpr int KC = I::KC, LDK = I::LDK, PART = I::PART, NI = I::BYTES / 1024;
-  __shared__ __attribute__((aligned(16))) uint16_t sB[2][I::ELEMS];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int r = lane & 31, hf = lane >> 5;
-  const int64_t b = blockIdx.x;
-  const int64_t idx = b >> 3;
-  const int64_t rb = (idx / a.n_blocks) * 8 + (b & 7);  // XCD-aware: a row block's column blocks share an L2
-  const int nb = (int)(idx % a.n_blocks);
-  if (rb >= a.row_blocks) return;
-  const int64_t M = a.M;
-  const int K = a.K, chunks = K / KC;
-  const int64_t m = rb * kPBM + wv * 32 + r;
-  const float* xrow = a.X + (m < M ? m : M - 1) * a.ldx + 4 * hf;  // rows past M re-read row M-1 (never stored)
-  // buffer_load ... lds (MUBUF), not global_load_lds: the compiler counts a FLAT LDS-DMA as a
-  // pending LDS access, and every LDS-read wait behind it became lgkmcnt(0) -- the ds_reads of
-  // step i + 1 could not overlap step i's MFMAs.  A MUBUF LDS-DMA is tracked on vmcnt only.
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint16_t*>(img + (int64_t)nb * chunks * I::ELEMS), 0, chunks * I::BYTES, 0x00020000);
-  auto issue = [&](int c, int buf) {  // chunk c's three images -> sB[buf], 1 KB per wave instruction
-    const int src = c * I::BYTES + lane * 16;
-    char* dst = reinterpret_cast<char*>(sB[buf]);
-    for (int i = wv; i < NI; i += 8)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(dst + i * 1024), 16,
-                                               src + i * 1024, 0, 0, 0);
-  };
-  float4 xa[4], xn[4];
-#pragma unroll
-  for (int g = 0; g < 4; ++g) xa[g] = ld4(xrow + 8 * g);
-  f32x16 acc[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) acc[t] = f32x16{};
-  issue(0, 0);
-  __syncthreads();  // vmcnt(0): chunk 0 and the first x fragments have landed
-  for (int c = 0; c < chunks; ++c) {
-    const int buf = c & 1;
-    const bool more = c + 1 < chunks;
-    if (more) {
-      issue(c + 1, buf ^ 1);  // the buffer every wave finished reading before the last barrier
-#pragma unroll
-      for (int g = 0; g < 4; ++g) xn[g] = ld4(xrow + (c + 1) * KC + 8 * g);
-    }
-    const uint16_t* sb = sB[buf];
-    auto read_b = [&](int i, split::u32x4 (&f)[3]) {
-      const int off = (32 * (i % NT) + r) * LDK + 16 * (i / NT) + 8 * hf;
-#pragma unroll
-      for (int p = 0; p < 3; ++p) f[p] = *reinterpret_cast<const split::u32x4*>(&sb[p * PART + off]);
-    };
-    // B fragments in two register sets used alternately (no copy between them, so the register
-    // allocator cannot merge them): the reads of step i + 1 issue before the six MFMAs of step i
-    // and have those ~190 cycles to land (with one merged set they were scheduled after the
-    // step's fifth MFMA and the next step waited on the LDS latency)
-    split::u32x4 fx[3], fb[2][3];
-    read_b(0, fb[0]);
-#pragma unroll
-    for (int i = 0; i < (KC / 16) * NT; ++i) {
-      const int u = i / NT, t = i % NT;
-      if (t == 0) split::split3(xa[2 * u], xa[2 * u + 1], fx[0], fx[1], fx[2]);
-      if (i + 1 < (KC / 16) * NT) read_b(i + 1, fb[(i + 1) & 1]);
-      acc[t] = split::mfma32_x6(fx, fb[i & 1], acc[t]);
-      // order inside the step: the next step's three LDS reads first, then the six MFMAs
-      if (i + 1 < (KC / 16) * NT) __builtin_amdgcn_sched_group_barrier(0x0100, 3, 0);
-      __builtin_amdgcn_sched_group_barrier(0x0008, 6, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    __syncthreads();  // vmcnt(0): chunk c + 1 has landed; every wave is done with sB[buf]
-    if (more) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) xa[g] = xn[g];
-    }
-  }
-  const int64_t row0 = rb * kPBM + wv * 32;
-  const int n0 = nb * I::BN;
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const int col = n0 + 32 * t + r;
-    const float bv = a.bias != nullptr ? a.bias[col] : 0.f;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int64_t row = row0 + (q & 3) + 8 * (q >> 2) + 4 * hf;
-      if (row < M) a.Y[row * a.ldy + col] = fmaf(a.alpha, acc[t][q], bv);
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------
 // NN GEMM on the fp16 matrix cores through the scaled two-term split (ppgat_split.h): three
 // MFMAs per product instead of six.  B is pre-split once per call with a power-of-two scale per
 // column (k_colscale16 + k_nnh_presplit: two fp16 images per (column block, k chunk), the same
-// 80-B rows and permuted reduction order as the bf16 images).  X streams in 32-deep chunks, so a
+// 80-B rows and permuted reduction order as the lab build's bf16 images).  X streams in 32-deep chunks, so a
 // row's scale is set ONLINE: by the first chunk in which the row is nonzero (largest |x| s in
 // [2^9, 2^10)), and lowered only when a later chunk would reach 2^15 (fp16 overflows at 65,520,
 // so 32x headroom) -- then that row's accumulators are multiplied by the exact power of two
@@ -613,300 +484,22 @@ __global__ void __launch_bounds__(256) k_nnh_presplit(const float* __restrict__ 
 
 constexpr int kNnhRank = 8;  // rank terms the fused epilogue keeps in registers
 
-template <int NT, bool RK>
-__global__ void __launch_bounds__(512, 1) k_gemm_nnh(NnArg a, const uint16_t* __restrict__ img,
-                                                     const int* __restrict__ ecol) {
-  using I = NnhImg<NT>;
-  constexpr int KC = I::KC, LDK = I::LDK, PART = I::PART, NI = I::BYTES / 1024;
-  __shared__ __attribute__((aligned(16))) uint16_t sB[2][I::ELEMS];
-  __shared__ __attribute__((aligned(16))) float sF[8][32];  // per wave: a factor per row (rescale, epilogue)
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int r = lane & 31, hf = lane >> 5;
-  const int64_t b = blockIdx.x;
-  const int64_t idx = b >> 3;
-  const int64_t rb = (idx / a.n_blocks) * 8 + (b & 7);  // XCD-aware: a row block's column blocks share an L2
-  const int nb = (int)(idx % a.n_blocks);
-  if (rb >= a.row_blocks) return;
-  const int64_t M = a.M;
-  const int K = a.K, chunks = K / KC;
-  const int64_t m = rb * kPBM + wv * 32 + r;
-  const float* xrow = a.X + (m < M ? m : M - 1) * a.ldx + 4 * hf;  // rows past M re-read row M-1 (never stored)
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint16_t*>(img + (int64_t)nb * chunks * I::ELEMS), 0, chunks * I::BYTES, 0x00020000);
-  auto issue = [&](int c, int buf) {  // chunk c's two images -> sB[buf], 1 KB per wave instruction
-    const int src = c * I::BYTES + lane * 16;
-    char* dst = reinterpret_cast<char*>(sB[buf]);
-    for (int i = wv; i < NI; i += 8)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(dst + i * 1024), 16,
-                                               src + i * 1024, 0, 0, 0);
-  };
-  float4 xa[4], xn[4];
-#pragma unroll
-  for (int g = 0; g < 4; ++g) xa[g] = ld4(xrow + 8 * g);
-  f32x16 acc[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) acc[t] = f32x16{};
-  int erow = 0;
-  bool set = false;  // the row has had a nonzero element (its scale is fixed until an overflow)
-  issue(0, 0);
-  __syncthreads();  // vmcnt(0): chunk 0 and the first x fragments have landed
-  for (int c = 0; c < chunks; ++c) {
-    const int buf = c & 1;
-    const bool more = c + 1 < chunks;
-    if (more) {
-      issue(c + 1, buf ^ 1);  // the buffer every wave finished reading before the last barrier
-#pragma unroll
-      for (int g = 0; g < 4; ++g) xn[g] = ld4(xrow + (c + 1) * KC + 8 * g);
-    }
-    const float s = split::row_scale_online<NT>(xa, erow, set, acc, sF[wv], r, hf);  // chunk c's row scales
-    const uint16_t* sb = sB[buf];
-    auto read_b = [&](int i, split::u32x4 (&f)[2]) {
-      const int off = (32 * (i % NT) + r) * LDK + 16 * (i / NT) + 8 * hf;
-#pragma unroll
-      for (int p = 0; p < 2; ++p) f[p] = *reinterpret_cast<const split::u32x4*>(&sb[p * PART + off]);
-    };
-    // two fragment sets used alternately; each step issues the next step's two LDS reads before
-    // its three MFMAs (see k_gemm_nnp)
-    split::u32x4 fx[2], fb[2][2];
-    read_b(0, fb[0]);
-#pragma unroll
-    for (int i = 0; i < (KC / 16) * NT; ++i) {
-      const int u = i / NT, t = i % NT;
-      if (t == 0) split::split2h(xa[2 * u], xa[2 * u + 1], s, fx[0], fx[1]);
-      if (i + 1 < (KC / 16) * NT) read_b(i + 1, fb[(i + 1) & 1]);
-      acc[t] = split::mfma32_h3(fx, fb[i & 1], acc[t]);
-      if (i + 1 < (KC / 16) * NT) __builtin_amdgcn_sched_group_barrier(0x0100, 2, 0);
-      __builtin_amdgcn_sched_group_barrier(0x0008, 3, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    __syncthreads();  // vmcnt(0): chunk c + 1 has landed; every wave is done with sB[buf]
-    if (more) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) xa[g] = xn[g];
-    }
-  }
-  float fr[16];  // unscale: 1 / (s_row s_col), both exact powers of two
-  split::row_unscale(erow, sF[wv], r, hf, fr);
-  const int64_t row0 = rb * kPBM + wv * 32;
-  const int n0 = nb * I::BN;
-  if constexpr (RK) {
-    // + S A (nv <= kNnhRank): this lane's columns of A in registers, each row's S terms loaded
-    // once (broadcast over the 32 lanes of the row), the terms added in v order after alpha, bias
-    const int nv = a.nv;
-    float ra[NT][kNnhRank], bv[NT], ic[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const int col = n0 + 32 * t + r;
-      bv[t] = a.bias != nullptr ? a.bias[col] : 0.f;
-      ic[t] = ldexpf(a.alpha, -ecol[col]);
-#pragma unroll
-      for (int v = 0; v < kNnhRank; ++v) ra[t][v] = v < nv ? a.rA[v * a.ldra + col] : 0.f;
-    }
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int64_t row = row0 + (q & 3) + 8 * (q >> 2) + 4 * hf;
-      const int64_t rr = row < M ? row : M - 1;
-      float sv[kNnhRank];
-#pragma unroll
-      for (int v = 0; v < kNnhRank; ++v) sv[v] = v < nv ? a.rS[rr * a.ldrs + v] : 0.f;
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        float y = fmaf(acc[t][q] * fr[q], ic[t], bv[t]);
-#pragma unroll
-        for (int v = 0; v < kNnhRank; ++v)
-          if (v < nv) y = fmaf(sv[v], ra[t][v], y);
-        if (row < M) a.Y[row * a.ldy + n0 + 32 * t + r] = y;
-      }
-    }
-  } else {
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const int col = n0 + 32 * t + r;
-      const float bv = a.bias != nullptr ? a.bias[col] : 0.f;
-      const float ic = ldexpf(a.alpha, -ecol[col]);
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const int64_t row = row0 + (q & 3) + 8 * (q >> 2) + 4 * hf;
-        if (row < M) a.Y[row * a.ldy + col] = fmaf(acc[t][q] * fr[q], ic, bv);
-      }
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------
-// k_gemm_nnh2: k_gemm_nnh's arithmetic (the same products in the same order: bitwise equal
-// results) with a deeper pipeline.  In k_gemm_nnh the compiler waits for the whole vector-memory
-// queue twice per 32-deep chunk -- before the first LDS read after an LDS-DMA issue (it cannot
-// tell the DMA target from the buffer being read) and at every __syncthreads (its workgroup
-// fence) -- so the next chunk's X rows, streamed from HBM one chunk ahead, had only part of a
-// chunk to arrive (MFMA busy 0.41, 46 % of the wave cycles waiting; profiles/r03/v27_nnh_pmc.json).
-// Here:
-//  * B chunks go to LDS by LDS-DMA issued in inline asm (the compiler sees no memory access, so
-//    it adds no wait before LDS reads), three buffers, issued two chunks ahead;
-//  * X rows stream two chunks ahead in two register sets; a chunk's rows are scaled and split
-//    into their fp16 fragments at the top of the chunk, which frees the set for chunk c + 2;
-//  * the chunk barrier is a bare s_barrier after an explicit vmcnt wait for exactly this
-//    wave's DMA of chunk c + 1 (the only operation the barrier must cover: everything issued
-//    after it -- X of c + 1, DMA and X of c + 2 -- stays in flight).
-// Global issue order per wave: DMA(0) X(0) DMA(1) X(1) | chunk c: DMA(c+2) X(c+2) ...
+// k_gemm_nnh3: the pipelined main loop of ppgat_nnh_pipe.h (nnh3_loop) -- B chunks by LDS-DMA two
+// chunks ahead, the next chunk prepared inside the current chunk's MFMA sequence -- and the
+// epilogue.  The same products in the same order as its predecessors k_gemm_nnh and k_gemm_nnh2
+// (lab/ppgat_xform_lab.h; bitwise equal results, tests/test_gpu_gemm_f16.py).
 // ---------------------------------------------------------------------------
-
-// LAB (diagnostics only, lab builds -DPPGAT_LAB_BUILD=1, never in libppgat.so; PPGAT_NNH2_LAB;
-// results wrong), bits: 1 = no X loads after the first
-// two chunks (registers reused), 2 = no B DMA after the first two chunks (LDS reused), 4 = no
-// epilogue stores (a row is stored only if its first accumulator is NaN), 8 = no chunk barrier
-template <int NT, bool RK, int LAB = 0>
-__global__ void __launch_bounds__(512, 1) k_gemm_nnh2(NnArg a, const uint16_t* __restrict__ img,
-                                                      const int* __restrict__ ecol) {
-  using I = NnhImg<NT>;
-  constexpr int KC = I::KC, LDK = I::LDK, PART = I::PART, NI = I::BYTES / 1024;
-  __shared__ __attribute__((aligned(16))) uint16_t sB[3][I::ELEMS];
-  __shared__ __attribute__((aligned(16))) float sF[8][32];  // per wave: a factor per row (rescale, epilogue)
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int r = lane & 31, hf = lane >> 5;
-  const int64_t b = blockIdx.x;
-  const int64_t idx = b >> 3;
-  const int64_t rb = (idx / a.n_blocks) * 8 + (b & 7);  // XCD-aware: a row block's column blocks share an L2
-  const int nb = (int)(idx % a.n_blocks);
-  if (rb >= a.row_blocks) return;
-  const int64_t M = a.M;
-  const int K = a.K, chunks = K / KC;
-  const int64_t m = rb * kPBM + wv * 32 + r;
-  const float* xrow = a.X + (m < M ? m : M - 1) * a.ldx + 4 * hf;  // rows past M re-read row M-1 (never stored)
-  // buffer resource of this column block's images (stride 0, raw bytes), wave-uniform
-  const uint64_t base = reinterpret_cast<uint64_t>(img + (int64_t)nb * chunks * I::ELEMS);
-  const i32x4 rsrc = {__builtin_amdgcn_readfirstlane((int)(uint32_t)base),
-                      __builtin_amdgcn_readfirstlane((int)((base >> 32) & 0xffff)),
-                      __builtin_amdgcn_readfirstlane(chunks * I::BYTES), 0x00020000};
-  const uint32_t lds0 = (uint32_t)reinterpret_cast<uintptr_t>(&sB[0][0]);
-  const uint32_t voff = (uint32_t)lane * 16u;
-  constexpr int ND = (NI + 7) / 8;  // DMA instructions of waves 0 .. (NI % 8) - 1 (one fewer for the rest)
-  const bool full = (NI % 8 == 0) || wv < NI % 8;
-  auto issue = [&](int c) {  // chunk c's two images -> sB[c % 3], 1 KB per wave instruction
-    const uint32_t dst = lds0 + (uint32_t)((c % 3) * I::ELEMS * 2);
-    for (int i = wv; i < NI; i += 8) dma_lds16(rsrc, dst + i * 1024, voff, (uint32_t)(c * I::BYTES + i * 1024));
-  };
-  auto loadx = [&](int c, float4 (&x)[4]) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) x[g] = ld4(xrow + c * KC + 8 * g);
-  };
-  f32x16 acc[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) acc[t] = f32x16{};
-  int erow = 0;
-  bool set = false;  // the row has had a nonzero element (its scale is fixed until an overflow)
-  // chunks is even (>= 2; the launcher checks): the loop below runs chunk pairs (xA, xB) and
-  // every chunk loads an X set, the last two re-reading chunk chunks - 1, so the compiler sees
-  // the same four loads per chunk on every path and waits for exactly the set it reads
-  float4 xA[4], xB[4];
-  issue(0);
-  loadx(0, xA);
-  issue(1);
-  loadx(1, xB);
-  if (full) wait_vm<4 + ND + 4>(); else wait_vm<4 + ND - 1 + 4>();  // DMA(0) has landed
-  __builtin_amdgcn_s_barrier();
-
-  auto body = [&](const int c, float4 (&xc)[4]) {
-    // X(c): this chunk's row scales and fp16 fragments (both k steps), then the set is free
-    const float s = split::row_scale_online<NT>(xc, erow, set, acc, sF[wv], r, hf);
-    split::u32x4 fx[2][2];
-    split::split2h(xc[0], xc[1], s, fx[0][0], fx[0][1]);
-    split::split2h(xc[2], xc[3], s, fx[1][0], fx[1][1]);
-    const bool ahead = c + 2 < chunks;
-    if (ahead && !(LAB & 2)) issue(c + 2);
-    if (!(LAB & 1)) loadx(ahead ? c + 2 : chunks - 1, xc);
-    const uint16_t* sb = sB[c % 3];
-    auto read_b = [&](int i, split::u32x4 (&f)[2]) {
-      const int off = (32 * (i % NT) + r) * LDK + 16 * (i / NT) + 8 * hf;
-#pragma unroll
-      for (int p = 0; p < 2; ++p) f[p] = *reinterpret_cast<const split::u32x4*>(&sb[p * PART + off]);
-    };
-    split::u32x4 fb[2][2];
-    read_b(0, fb[0]);
-#pragma unroll
-    for (int i = 0; i < (KC / 16) * NT; ++i) {
-      const int u = i / NT, t = i % NT;
-      if (i + 1 < (KC / 16) * NT) read_b(i + 1, fb[(i + 1) & 1]);
-      acc[t] = split::mfma32_h3(fx[u], fb[i & 1], acc[t]);
-      if (i + 1 < (KC / 16) * NT) __builtin_amdgcn_sched_group_barrier(0x0100, 2, 0);
-      __builtin_amdgcn_sched_group_barrier(0x0008, 3, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    // DMA(c + 1) must have landed before any wave reads it, and every wave must be done with
-    // sB[c % 3] before chunk c + 3's DMA (issued in chunk c + 1) overwrites it.  Issued after
-    // DMA(c + 1): X(c + 1), and in this chunk DMA(c + 2) (if any) and an X set.
-    if (LAB) {
-      wait_vm<0>();
-    } else if (ahead) {
-      if (full) wait_vm<4 + ND + 4>(); else wait_vm<4 + ND - 1 + 4>();
-    } else {
-      wait_vm<4 + 4>();
-    }
-    if (!(LAB & 8)) __builtin_amdgcn_s_barrier();
-  };
-  for (int c = 0; c < chunks; c += 2) {
-    body(c, xA);
-    body(c + 1, xB);
-  }
-  float fr[16];  // unscale: 1 / (s_row s_col), both exact powers of two
-  split::row_unscale(erow, sF[wv], r, hf, fr);
-  const int64_t row0 = rb * kPBM + wv * 32;
-  const int n0 = nb * I::BN;
-  if constexpr (RK) {
-    const int nv = a.nv;
-    float ra[NT][kNnhRank], bv[NT], ic[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const int col = n0 + 32 * t + r;
-      bv[t] = a.bias != nullptr ? a.bias[col] : 0.f;
-      ic[t] = ldexpf(a.alpha, -ecol[col]);
-#pragma unroll
-      for (int v = 0; v < kNnhRank; ++v) ra[t][v] = v < nv ? a.rA[v * a.ldra + col] : 0.f;
-    }
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int64_t row = row0 + (q & 3) + 8 * (q >> 2) + 4 * hf;
-      const int64_t rr = row < M ? row : M - 1;
-      float sv[kNnhRank];
-#pragma unroll
-      for (int v = 0; v < kNnhRank; ++v) sv[v] = v < nv ? a.rS[rr * a.ldrs + v] : 0.f;
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        float y = fmaf(acc[t][q] * fr[q], ic[t], bv[t]);
-#pragma unroll
-        for (int v = 0; v < kNnhRank; ++v)
-          if (v < nv) y = fmaf(sv[v], ra[t][v], y);
-        if (row < M) a.Y[row * a.ldy + n0 + 32 * t + r] = y;
-      }
-    }
-  } else {
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const int col = n0 + 32 * t + r;
-      const float bv = a.bias != nullptr ? a.bias[col] : 0.f;
-      const float ic = ldexpf(a.alpha, -ecol[col]);
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const int64_t row = row0 + (q & 3) + 8 * (q >> 2) + 4 * hf;
-        if (row < M && (!(LAB & 4) || acc[0][q] != acc[0][q])) a.Y[row * a.ldy + col] = fmaf(acc[t][q] * fr[q], ic, bv);
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// k_gemm_nnh3: k_gemm_nnh2's pipeline with the next chunk prepared inside the current chunk's
-// MFMA sequence (ppgat_nnh_pipe.h: nnh3_loop), same products in the same order as k_gemm_nnh.
-// ---------------------------------------------------------------------------
-// E4 (lab builds, PPGAT_NNH_E4=1): the epilogue without rank terms through a per-wave LDS
+// libppgat.so instantiates NT and RK only; XT, E4 and OCC are the lab build's measured variants,
+// which the lab tests pin bitwise against the product kernel.
+// XT (lab, PPGAT_NNH2=6): X loaded coalesced and transposed through LDS (see nnh3_loop).
+// E4 (lab, PPGAT_NNH_E4=1): the epilogue without rank terms through a per-wave LDS
 // transpose -- each lane's column of 16 rows is written to the (now idle) B buffers and read back
 // as float4 pieces of rows, so a wave stores its 32 x 32 block per column tile in 4 float4
 // instructions (8 rows x 128 B each) instead of 16 scalar ones; the same values (same bits).
 // OCC (lab, PPGAT_NNH_OCC2=1 with NT = 4): at least OCC waves per SIMD (HIP's launch_bounds), i.e. two
 // workgroups per CU at OCC = 4, so one's epilogue stores can run beside the other's products.
-template <int NT, bool RK, int BD = 1, bool PRIO = false, int LAB = 0, bool XT = false, bool E4 = false, int OCC = 1>
+template <int NT, bool RK, bool XT = false, bool E4 = false, int OCC = 1>
 __global__ void __launch_bounds__(512, OCC) k_gemm_nnh3(NnArg a, const uint16_t* __restrict__ img,
                                                       const int* __restrict__ ecol) {
   using I = NnhImg<NT>;
@@ -940,15 +533,14 @@ __global__ void __launch_bounds__(512, OCC) k_gemm_nnh3(NnArg a, const uint16_t*
 #pragma unroll
       for (int j = 0; j < 4; ++j) x[j] = ld4(xr[j] + c * KC);
     };
-    nnh3_loop<NT, BD, PRIO, LAB, true>(img + (int64_t)nb * chunks * I::ELEMS, sB, chunks, loadx, acc, erow, sF[wv],
-                                       wv, lane, sX[wv]);
+    nnh3_loop<NT, true>(img + (int64_t)nb * chunks * I::ELEMS, sB, chunks, loadx, acc, erow, sF[wv], wv, lane,
+                        sX[wv]);
   } else {
     auto loadx = [&](int c, float4 (&x)[4]) {
 #pragma unroll
       for (int g = 0; g < 4; ++g) x[g] = ld4(xrow + c * KC + 8 * g);
     };
-    nnh3_loop<NT, BD, PRIO, LAB>(img + (int64_t)nb * chunks * I::ELEMS, sB, chunks, loadx, acc, erow, sF[wv], wv,
-                                 lane);
+    nnh3_loop<NT>(img + (int64_t)nb * chunks * I::ELEMS, sB, chunks, loadx, acc, erow, sF[wv], wv, lane);
   }
   float fr[16];  // unscale: 1 / (s_row s_col), both exact powers of two
   split::row_unscale(erow, sF[wv], r, hf, fr);
@@ -1014,7 +606,7 @@ __global__ void __launch_bounds__(512, OCC) k_gemm_nnh3(NnArg a, const uint16_t*
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
         const int64_t row = row0 + (q & 3) + 8 * (q >> 2) + 4 * hf;
-        if (row < M && (!(LAB & 4) || acc[0][q] != acc[0][q])) a.Y[row * a.ldy + col] = fmaf(acc[t][q] * fr[q], ic, bv);
+        if (row < M) a.Y[row * a.ldy + col] = fmaf(acc[t][q] * fr[q], ic, bv);
       }
     }
   }
@@ -2592,63 +2184,37 @@ int gemm_nn_splits(int64_t M, int K, int N) {
   return s;
 }
 
-// the three bf16 images of B [K x N] (bmode 0: B[k][n] = B[k ldb + n]; 1: B[n ldb + k]) per
-// (column block of 32 nt columns, 32-deep k chunk), in the LDS layout the split kernels read
-#ifdef PPGAT_LAB_BUILD
-hipError_t nnx_presplit(const float* B, int64_t ldb, int bmode, int K, int N, int nt, uint16_t* img, hipStream_t st) {
-  const int64_t groups = (int64_t)N * (K / 4);
-  const unsigned gp = (unsigned)((groups + 255) / 256);
-  if (groups <= 0) return hipSuccess;
-  if (nt == 8) {
-    if (bmode == 0) hipLaunchKernelGGL((k_nnx_presplit<8, 0>), dim3(gp), dim3(256), 0, st, B, ldb, K, N, img);
-    else hipLaunchKernelGGL((k_nnx_presplit<8, 1>), dim3(gp), dim3(256), 0, st, B, ldb, K, N, img);
-  } else {
-    if (bmode == 0) hipLaunchKernelGGL((k_nnx_presplit<4, 0>), dim3(gp), dim3(256), 0, st, B, ldb, K, N, img);
-    else hipLaunchKernelGGL((k_nnx_presplit<4, 1>), dim3(gp), dim3(256), 0, st, B, ldb, K, N, img);
-  }
-  return hipGetLastError();
-}
-
-#endif
-
+// bytes of the three bf16 images of B [K x N] per (column block of 32 nt columns, 32-deep k
+// chunk); only the lab build writes them (nnx_presplit), both builds size workspaces by them
 size_t nnx_image_bytes(int K, int N, int nt) {
   const size_t img = nt == 8 ? (size_t)NnpImg<8>::BYTES : (size_t)NnpImg<4>::BYTES;
   return (size_t)(N / (32 * nt)) * (size_t)(K / 32) * img;
 }
 
-// the pre-split path: large M, K % 32 == 0.  libppgat.so runs it on k_gemm_nnh3 only, which takes
-// the K chunks in pairs: other shapes go to the general x6 kernel (k_gemm_nnx).  The superseded
-// generations -- k_gemm_nnh (any chunk count), k_gemm_nnh2 and the bf16 x6 k_gemm_nnp
-// (PPGAT_GEMM_NNP / PPGAT_GEMM_F16 / PPGAT_NNH2) -- exist only in the lab build (make lab).
-static bool nnp_ok(int64_t M, int K, int N) {
 #ifdef PPGAT_LAB_BUILD
-  static const bool off = [] {
-    const char* e = getenv("PPGAT_GEMM_NNP");
-    return e && strcmp(e, "0") == 0;
-  }();
-  if (off) return false;
-#else
-  if ((K / kGBK) % 2 != 0) return false;
+#include "lab/ppgat_xform_lab.h"  // the superseded kernel generations, their switches and launches
 #endif
-  return gemm_split_enabled() && M >= 4 * kPBM && K % 32 == 0 && N % 128 == 0 && gemm_nn_splits(M, K, N) == 1;
+
+// the pre-split path: large M, K % 32 == 0, on k_gemm_nnh3, which takes the K chunks in pairs:
+// other shapes go to the general x6 kernel (k_gemm_nnx)
+static bool nnp_ok(int64_t M, int K, int N) {
+  bool chunks_ok = (K / kGBK) % 2 == 0;
+#ifdef PPGAT_LAB_BUILD
+  chunks_ok = chunks_ok || lab::odd_chunks_ok();
+#endif
+  return chunks_ok && gemm_split_enabled() && M >= 4 * kPBM && K % 32 == 0 && N % 128 == 0 &&
+         gemm_nn_splits(M, K, N) == 1;
 }
 
 static size_t nnp_image_bytes(int K, int N) { return nnx_image_bytes(K, N, N % 256 == 0 ? 8 : 4); }
 
-// the fp16 two-term family on the pre-split path; lab builds: PPGAT_GEMM_F16=0 runs the bf16 x6 k_gemm_nnp
+// the fp16 two-term family (the pre-split NN path, k_gemm_tnh): always on in libppgat.so
 static bool nnh_enabled() {
 #ifdef PPGAT_LAB_BUILD
-  static const bool off = [] {
-    const char* e = getenv("PPGAT_GEMM_F16");
-    return e && strcmp(e, "0") == 0;
-  }();
-  return !off;
-#else
-  return true;
+  if (lab::f16_off()) return false;
 #endif
+  return true;
 }
-
-bool gemm_f16_enabled() { return nnh_enabled(); }
 
 size_t nnh_image_bytes(int K, int N, int nt) {
   const size_t img = nt == 8 ? (size_t)NnhImg<8>::BYTES : (size_t)NnhImg<4>::BYTES;
@@ -2673,39 +2239,6 @@ hipError_t nnh_presplit(const float* B, int64_t ldb, int bmode, int K, int N, in
 #undef PPGAT_NNH_PRE
   return hipGetLastError();
 }
-
-// the NN fp16 two-term kernel: k_gemm_nnh3; in lab builds PPGAT_NNH2=0 k_gemm_nnh, =2 k_gemm_nnh2
-// (and k_fusion_fwdh3; the default: 2-3 % faster than k_gemm_nnh2 at config-5 shapes, profiles/
-// r04/v8_gemm5_nnh*.log).  All three compute the same products in the same order (bitwise equal,
-// tests/test_gpu_gemm_f16.py::test_nnh2_bitwise_equals_nnh, a lab test).  Read once per process.
-// The measured-negative nnh3 variants (4: B read two steps ahead, 5: + s_setprio, 6: X through
-// LDS; all within 1-2 % of 3, v8/v22_gemm5_nnh*.log) and the diagnostic lab kernels
-// (PPGAT_NNH2_LAB: parts of the loop removed, results WRONG) exist only in a lab build:
-// tools/build_variants.sh ppgat_xform.hip lab:"-DPPGAT_LAB_BUILD=1" -- never in libppgat.so.
-int nnh_pipeline_variant() {
-#ifdef PPGAT_LAB_BUILD
-  static const int v = [] {
-    const char* e = getenv("PPGAT_NNH2");
-    if (e && strcmp(e, "0") == 0) return 1;
-    if (e && strcmp(e, "2") == 0) return 2;
-    if (e && (strcmp(e, "4") == 0 || strcmp(e, "5") == 0 || strcmp(e, "6") == 0)) return e[0] - '0';
-    return 3;
-  }();
-  return v;
-#else
-  return 3;
-#endif
-}
-
-#ifdef PPGAT_LAB_BUILD
-static int nnh2_lab() {
-  static const int lab = [] {
-    const char* e = getenv("PPGAT_NNH2_LAB");
-    return e ? atoi(e) : 0;
-  }();
-  return lab;
-}
-#endif
 
 static size_t nnq_bytes(int K, int N) {  // image + column exponents, either family
   const int nt = N % 256 == 0 ? 8 : 4;
@@ -2732,119 +2265,29 @@ hipError_t gemm_nn(const float* X, int64_t ldx, int64_t M, int K, const float* B
   a.rS = rS; a.ldrs = ldrs; a.nv = nv; a.rA = rA; a.ldra = ldra;
   a.X = X; a.ldx = ldx; a.M = M; a.K = K; a.B = B; a.ldb = ldb; a.N = N; a.alpha = alpha; a.bias = bias;
   a.Y = Y; a.ldy = ldy;
-  if (ws != nullptr && nnp_ok(M, K, N)) {  // B pre-split once, then the glds-staged kernel
+  if (ws != nullptr && nnp_ok(M, K, N)) {  // B pre-split once, then k_gemm_nnh3
     const bool w8 = N % 256 == 0;
     uint16_t* img = static_cast<uint16_t*>(ws);
     a.row_blocks = (M + kPBM - 1) / kPBM;
     a.n_blocks = N / (w8 ? 256 : 128);
     a.splits = 1;
     const unsigned grid = (unsigned)((a.row_blocks + 7) / 8 * 8 * a.n_blocks);
-    if (nnh_enabled()) {  // fp16 two-term split: three MFMAs per product
-      int* ecol = reinterpret_cast<int*>(reinterpret_cast<char*>(ws) + align_up(nnh_image_bytes(K, N, w8 ? 8 : 4)));
-      hipError_t e = nnh_presplit(B, ldb, bmode, K, N, w8 ? 8 : 4, img, ecol, st);
-      if (e != hipSuccess) return e;
-      if (nnh_pipeline_variant() >= 3 && (K / kGBK) % 2 == 0) {  // k_gemm_nnh3 runs chunk pairs
-        const int v = nnh_pipeline_variant();
 #ifdef PPGAT_LAB_BUILD
-        if (const int lab = nnh2_lab(); lab > 0 && nv == 0 && w8) {  // diagnostics (results wrong)
-#define PPGAT_LAB3(L) \
-  if (lab == L) hipLaunchKernelGGL((k_gemm_nnh3<8, false, 1, false, L>), dim3(grid), dim3(512), 0, st, a, img, ecol)
-          PPGAT_LAB3(1); PPGAT_LAB3(3); PPGAT_LAB3(7); PPGAT_LAB3(23); PPGAT_LAB3(39); PPGAT_LAB3(55);
-#undef PPGAT_LAB3
-          return hipGetLastError();
-        }
+    if (hipError_t e; lab::gemm_nn_presplit(a, bmode, w8, grid, ws, st, &e)) return e;
 #endif
-#define PPGAT_NNH3(BD, PR, XT)                                                                                   \
-  do {                                                                                                           \
-    if (nv > 0) {                                                                                                \
-      if (w8) hipLaunchKernelGGL((k_gemm_nnh3<8, true, BD, PR, 0, XT>), dim3(grid), dim3(512), 0, st, a, img, ecol); \
-      else hipLaunchKernelGGL((k_gemm_nnh3<4, true, BD, PR, 0, XT>), dim3(grid), dim3(512), 0, st, a, img, ecol);    \
-    } else if (w8) {                                                                                             \
-      hipLaunchKernelGGL((k_gemm_nnh3<8, false, BD, PR, 0, XT>), dim3(grid), dim3(512), 0, st, a, img, ecol);        \
-    } else {                                                                                                     \
-      hipLaunchKernelGGL((k_gemm_nnh3<4, false, BD, PR, 0, XT>), dim3(grid), dim3(512), 0, st, a, img, ecol);        \
-    }                                                                                                            \
-  } while (0)
-#ifdef PPGAT_LAB_BUILD
-        static const bool e4 = [] {
-          const char* e = getenv("PPGAT_NNH_E4");
-          return e != nullptr && atoi(e) == 1;
-        }();
-        static const bool occ2 = [] {  // two workgroups per CU on the 128-column tile (<= 128 VGPRs)
-          const char* e = getenv("PPGAT_NNH_OCC2");
-          return e != nullptr && atoi(e) == 1;
-        }();
-        if (occ2 && nv == 0) {
-          NnArg b2 = a;
-          b2.n_blocks = N / 128;
-          const unsigned g2 = (unsigned)((b2.row_blocks + 7) / 8 * 8 * b2.n_blocks);
-          int* ecol4 = reinterpret_cast<int*>(reinterpret_cast<char*>(ws) + align_up(nnh_image_bytes(K, N, 4)));
-          if (w8) {  // re-split B for the 128-column tile
-            hipError_t e2 = nnh_presplit(B, ldb, bmode, K, N, 4, img, ecol4, st);
-            if (e2 != hipSuccess) return e2;
-          }
-          hipLaunchKernelGGL((k_gemm_nnh3<4, false, 1, false, 0, false, false, 4>), dim3(g2), dim3(512), 0, st, b2, img,
-                             w8 ? ecol4 : ecol);
-          return hipGetLastError();
-        }
-        if (e4 && nv == 0 && a.ldy % 4 == 0 && reinterpret_cast<uintptr_t>(Y) % 16 == 0) {
-          if (w8) hipLaunchKernelGGL((k_gemm_nnh3<8, false, 1, false, 0, false, true>), dim3(grid), dim3(512), 0, st, a, img, ecol);
-          else hipLaunchKernelGGL((k_gemm_nnh3<4, false, 1, false, 0, false, true>), dim3(grid), dim3(512), 0, st, a, img, ecol);
-          return hipGetLastError();
-        }
-        if (v == 4) PPGAT_NNH3(2, false, false);
-        else if (v == 5) PPGAT_NNH3(2, true, false);
-        else if (v == 6) PPGAT_NNH3(1, false, true);
-        else
-#endif
-        PPGAT_NNH3(1, false, false);
-        (void)v;
-#undef PPGAT_NNH3
-        return hipGetLastError();
-      }
-#ifdef PPGAT_LAB_BUILD
-      if (nnh_pipeline_variant() == 2 && (K / kGBK) % 2 == 0) {  // k_gemm_nnh2 runs chunk pairs
-#ifdef PPGAT_LAB_BUILD
-        if (const int lab = nnh2_lab(); lab > 0 && nv == 0 && w8) {
-#define PPGAT_LAB(L) \
-  if (lab == L) hipLaunchKernelGGL((k_gemm_nnh2<8, false, L>), dim3(grid), dim3(512), 0, st, a, img, ecol)
-          PPGAT_LAB(1); PPGAT_LAB(2); PPGAT_LAB(3); PPGAT_LAB(7); PPGAT_LAB(15);
-#undef PPGAT_LAB
-          return hipGetLastError();
-        }
-#endif
-        if (nv > 0) {
-          if (w8) hipLaunchKernelGGL((k_gemm_nnh2<8, true>), dim3(grid), dim3(512), 0, st, a, img, ecol);
-          else hipLaunchKernelGGL((k_gemm_nnh2<4, true>), dim3(grid), dim3(512), 0, st, a, img, ecol);
-        } else if (w8) {
-          hipLaunchKernelGGL((k_gemm_nnh2<8, false>), dim3(grid), dim3(512), 0, st, a, img, ecol);
-        } else {
-          hipLaunchKernelGGL((k_gemm_nnh2<4, false>), dim3(grid), dim3(512), 0, st, a, img, ecol);
-        }
-        return hipGetLastError();
-      }
-      if (nv > 0) {
-        if (w8) hipLaunchKernelGGL((k_gemm_nnh<8, true>), dim3(grid), dim3(512), 0, st, a, img, ecol);
-        else hipLaunchKernelGGL((k_gemm_nnh<4, true>), dim3(grid), dim3(512), 0, st, a, img, ecol);
-      } else if (w8) {
-        hipLaunchKernelGGL((k_gemm_nnh<8, false>), dim3(grid), dim3(512), 0, st, a, img, ecol);
-      } else {
-        hipLaunchKernelGGL((k_gemm_nnh<4, false>), dim3(grid), dim3(512), 0, st, a, img, ecol);
-      }
-      return hipGetLastError();
-#else
-      return hipErrorInvalidValue;  // unreachable: nnp_ok admits chunk pairs only
-#endif
-    }
-#ifdef PPGAT_LAB_BUILD
-    hipError_t e = nnx_presplit(B, ldb, bmode, K, N, w8 ? 8 : 4, img, st);
+    // fp16 two-term split: three MFMAs per product
+    int* ecol = reinterpret_cast<int*>(reinterpret_cast<char*>(ws) + align_up(nnh_image_bytes(K, N, w8 ? 8 : 4)));
+    hipError_t e = nnh_presplit(B, ldb, bmode, K, N, w8 ? 8 : 4, img, ecol, st);
     if (e != hipSuccess) return e;
-    if (w8) hipLaunchKernelGGL((k_gemm_nnp<8>), dim3(grid), dim3(512), 0, st, a, img);
-    else hipLaunchKernelGGL((k_gemm_nnp<4>), dim3(grid), dim3(512), 0, st, a, img);
+#define PPGAT_NNH3(NT_, RK_) \
+  hipLaunchKernelGGL((k_gemm_nnh3<NT_, RK_>), dim3(grid), dim3(512), 0, st, a, img, ecol)
+    if (nv > 0) {
+      if (w8) PPGAT_NNH3(8, true); else PPGAT_NNH3(4, true);
+    } else {
+      if (w8) PPGAT_NNH3(8, false); else PPGAT_NNH3(4, false);
+    }
+#undef PPGAT_NNH3
     return hipGetLastError();
-#else
-    return hipErrorInvalidValue;  // unreachable: the product's pre-split path is fp16
-#endif
   }
   a.row_blocks = (M + kGBM - 1) / kGBM;
   const int64_t padded = (a.row_blocks + 7) / 8 * 8;
@@ -2910,17 +2353,8 @@ static bool tnh_ok(int64_t M, int Ma, int Nb) {
 static int tnh_splits(int64_t M, int T) {  // one workgroup per CU: splits * tiles <= 256, >= 128 rows per split
   // two workgroup rounds per CU: the same time as one (3.96 vs 3.98 ms at the config-5 share,
   // profiles/r03/v16_tnh_*), half the rows per fp32 accumulator chain: 3.3e-6 vs 5.3e-6
-  // max-abs/max-abs on 1.875M-row reductions (fp32 MFMA kernel: 3.5e-6).  PPGAT_TNH_WAVES
-  // overrides (lab builds).
-#ifdef PPGAT_LAB_BUILD
-  static const int waves = [] {
-    const char* e = getenv("PPGAT_TNH_WAVES");
-    const int v = e ? atoi(e) : 2;
-    return v >= 1 && v <= 16 ? v : 2;
-  }();
-#else
+  // max-abs/max-abs on 1.875M-row reductions (fp32 MFMA kernel: 3.5e-6)
   constexpr int waves = 2;
-#endif
   int s = 256 * waves / T;
   if (s < 1) s = 1;
   while (s > 1 && M / s < 4 * kTR) s /= 2;
@@ -2994,15 +2428,11 @@ hipError_t gemm_tn_big(const float* A, int64_t lda, const float* B, int64_t ldb,
     if (e == hipSuccess && !a_bound) e = colmax_bits(A, lda, M, Ma, mx, st);
     if (e == hipSuccess && !b_bound) e = colmax_bits(B, ldb, M, Nb, mx + Ma, st);
     if (e != hipSuccess) return e;
+    bool t256 = Ma % 256 == 0;  // the 256 x 256 tile, the same row splits (the same bits)
 #ifdef PPGAT_LAB_BUILD
-    static const bool t256 = [] {  // PPGAT_TNH256=0: the 128 x 256 tile everywhere (A/B runs)
-      const char* e = getenv("PPGAT_TNH256");
-      return !(e && strcmp(e, "0") == 0);
-    }();
-#else
-    constexpr bool t256 = true;
+    t256 = t256 && !lab::tnh256_off();
 #endif
-    if (t256 && Ma % 256 == 0) {  // the 256 x 256 tile, the same row splits (the same bits)
+    if (t256) {
       static const bool attr2 = [] {
         return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_tnh256),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTh2Lds) == hipSuccess;
@@ -3081,30 +2511,10 @@ hipError_t xgat_fwd(const ItemsArg& it, const int32_t* col, const int32_t* eid, 
                     const int32_t* hub_row, const int32_t* hub_ptr, int64_t n_hubs, hipStream_t st, unsigned* xmax) {
   const float inv_keep = p > 0.f ? 1.f / (1.f - p) : 1.f;
   const XItems its{it.row, it.beg, it.end, it.n_items, it.n_hub_items};
-#ifdef PPGAT_LAB_BUILD
-  static const int fu = [] {  // rows in flight per wave (PPGAT_FWDX_U: 2 / 3 / 4 / 5 / 6 / 8)
-    const char* e = getenv("PPGAT_FWDX_U");
-    return e ? atoi(e) : 4;
-  }();
-#define PPGAT_FWDX(U_)                                                                                               \
-  PPGAT_XH(H, hipLaunchKernelGGL((k_fwd_x<256, HH, U_>), dim3((unsigned)((it.n_items + 3) / 4)), dim3(256), 0, st, \
-                                 its, col, eid, x, ldx, s_src, s_dst, slope, p, inv_keep, seed, seed_in, agg, m, invl, \
-                                 partial, xmax))
-  if (it.n_items > 0) {
-    if (fu == 2) PPGAT_FWDX(2);
-    else if (fu == 3) PPGAT_FWDX(3);
-    else if (fu == 5) PPGAT_FWDX(5);
-    else if (fu == 6) PPGAT_FWDX(6);
-    else if (fu == 8) PPGAT_FWDX(8);
-    else PPGAT_FWDX(4);
-  }
-#undef PPGAT_FWDX
-#else
   if (it.n_items > 0)
     PPGAT_XH(H, hipLaunchKernelGGL((k_fwd_x<256, HH>), dim3((unsigned)((it.n_items + 3) / 4)), dim3(256), 0, st, its,
                                    col, eid, x, ldx, s_src, s_dst, slope, p, inv_keep, seed, seed_in, agg, m, invl,
                                    partial, xmax));
-#endif
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   (void)K;

@@ -43,15 +43,6 @@ for s in $STEPS; do
             (cd /tmp && run pmcdst_b 300 timeout -s KILL 240 rocprofv3 --pmc TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum TCC_REQ_sum --kernel-trace --output-format csv -d "$OUT/pmcdst_b" -o b -- python "$R/bench.py" --steps 3 --warmup 1 --graph off --cpu-baseline-seconds 0) && \
             python "$R/tools/pmc_kernel.py" "k_dst_sum<true>" "$OUT/pmcdst_a" "$OUT/pmcdst_b" > "$OUT/pmc_dst_sum.json" && \
             python "$R/tools/pmc_kernel.py" "k_bwd_src<" "$OUT/pmcdst_a" "$OUT/pmcdst_b" > "$OUT/pmc_bwd_src_tcc.json" ;;
-    dstlab) for a in ${DSTAUX:-0 2 17 19}; do
-              (cd /tmp && run "dstlab2_aux$a" 300 env PPGAT_LIB=$R/lab_build/libppgat.so PPGAT_DST_AUX=$a timeout -s KILL 240 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RD_UNCACHED_32B_sum --kernel-trace --output-format csv -d "$OUT/dstlab2_$a" -o p -- python "$R/bench.py" --steps 3 --warmup 1 --graph off --cpu-baseline-seconds 0) || exit 1
-              python "$R/tools/pmc_kernel.py" "k_dst_sum<true" "$OUT/dstlab2_$a" > "$OUT/dstlab2_aux$a.json"
-              if [ -n "${DST5:-}" ]; then
-                (cd /tmp && run "dstlab5_aux$a" 400 env PPGAT_LIB=$R/lab_build/libppgat.so PPGAT_DST_AUX=$a timeout -s KILL 360 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RD_UNCACHED_32B_sum --kernel-trace --output-format csv -d "$OUT/dstlab5_$a" -o p -- python -u "$R/bench.py" --config 5 --steps 2 --warmup 1 --graph off --cpu-baseline-seconds 0) || exit 1
-                python "$R/tools/pmc_kernel.py" "k_dst_sum_vh<" "$OUT/dstlab5_$a" > "$OUT/dstlab5_long_aux$a.json"
-                python "$R/tools/pmc_kernel.py" "k_dst_sum_vh_short" "$OUT/dstlab5_$a" > "$OUT/dstlab5_short_aux$a.json"
-              fi
-            done ;;
     e4lab) run gemm5_base 300 python tools/bench_gemm.py --cfg5 --iters 10 && \
            run gemm5_e4 300 env PPGAT_LIB=lab_build/libppgat.so PPGAT_NNH_E4=1 python tools/bench_gemm.py --cfg5 --iters 10 && \
            run bench5_e4 600 env PPGAT_LIB=lab_build/libppgat.so PPGAT_NNH_E4=1 python -u bench.py --full --config 5 --steps 10 --warmup 3 ;;
@@ -62,7 +53,6 @@ for s in $STEPS; do
            run tnpmc256 400 env GEMM_ARGS=--tn5 GEMM_TAG=_tn256 bash tools/gemm_pmc.sh && \
            python tools/pmc_kernel.py "k_gemm_tnh256" "$OUT/gemm_pmc_tn256/p1" "$OUT/gemm_pmc_tn256/p2" "$OUT/gemm_pmc_tn256/p3" > "$OUT/tn256_pmc.json" ;;
     nnhpmc) run "nnhpmc${NNHV:-3}" 500 env GEMM_ARGS=--cfg5 GEMM_TAG="_nnh${NNHV:-3}" PPGAT_NNH2="${NNHV:-3}" bash tools/gemm_pmc.sh ;;
-    nnhlab) for l in ${LABS:-0 1 2 3}; do run "nnhlab$l" 300 env PPGAT_LIB=lab_build/libppgat.so PPGAT_NNH2_LAB=$l python tools/bench_gemm.py --cfg5 --iters 10; done ;;
     probec2) for a in ${C2PROBES:-2:300 4:300 8:300 8:0}; do set -- ${a%%:*} ${a#*:}
               run "probec2_w$1_a$2" 300 python -u tools/scale_probe.py --world $1 --rank 0 --graph --streams --a2a-gbs $2 --steps 20 --warmup 5
             done ;;
@@ -72,7 +62,6 @@ for s in $STEPS; do
     bench) run bench 600 python bench.py --full $BENCH_ARGS ;;
     bench3) run bench_cfg3 600 python bench.py --full --config 3 --cpu-baseline-seconds 0 ;;
     copylab) run copy_lab 120 tools/copy_lab ;;
-    fwdxu) for u in ${FWDXU:-8 6 4}; do run "bench5_fwdx_u$u" 600 env PPGAT_LIB=lab_build/libppgat.so PPGAT_FWDX_U=$u python -u bench.py --full --config 5 --steps 5 --warmup 2 --graph off; done ;;
     bench5full) run bench_cfg5_full 1000 python -u bench.py --full --config 5 --scale 1 --steps ${FULL_STEPS:-3} --warmup 1 --graph ${FULL_GRAPH:-on} ;;
     prof5full) (cd /tmp && run rocprof_cfg5_full 1000 rocprofv3 --kernel-trace --stats -d "$OUT/prof5full" -o run --output-format csv -- python -u "$R/bench.py" --config 5 --scale 1 --steps 2 --warmup 1 --graph off) ;;
     bench5) run bench_cfg5 900 python -u bench.py --full --config 5 --steps 10 --warmup 3 ;;
