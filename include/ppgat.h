@@ -423,6 +423,48 @@ int ppgat_bpr_sample(const int64_t* user_ptr, const int32_t* items_sorted, const
                      const int64_t* n_eligible, int64_t n_items, int64_t n_triples, uint64_t seed, int64_t t0,
                      int64_t* u, int64_t* i, int64_t* j, int32_t* bad, void* stream);
 
+/* ---- BPR mini-batches: every positive x neg_per_pos ------------------------------------
+ * Replaces: sample_bpr_batches, scripts/train_lightgcn.py:160-179 (a Python loop over every
+ *   train interaction per epoch): users in order, each user's items in list order,
+ *   neg_per_pos negatives each, cut into batches of batch_size triples.
+ * Triple t in [t0, t0 + n_triples), t0 + n_triples <= nnz * neg_per_pos: p = t / neg_per_pos,
+ * u = the user whose range of user_ptr holds p, i = user_items[p] (the ORIGINAL order given
+ * to ppgat_bpr_sampler_prepare, which is the reference's enumeration order), j = the first
+ * draw d = 0, 1, ... of the counter stream (seed, t, d) that is not one of u's items
+ * (items_sorted of ppgat_bpr_sampler_prepare; same hash, range reduction, 1024-draw limit and
+ * *bad = 2 rule as ppgat_bpr_sample).  Batch b of an epoch: t0 = b * batch_size, n_triples =
+ * min(batch_size, nnz * neg_per_pos - t0); the (u, i) columns then equal the reference's
+ * batches exactly, j comes from the counter stream instead of Python's random. */
+int ppgat_bpr_sample_positives(const int64_t* user_ptr, const int32_t* user_items, const int32_t* items_sorted,
+                               int64_t n_users, int64_t nnz, int64_t n_items, int64_t neg_per_pos, int64_t n_triples,
+                               uint64_t seed, int64_t t0, int64_t* u, int64_t* i, int64_t* j, int32_t* bad,
+                               void* stream);
+
+/* ---- LightGCN propagation hop -------------------------------------------------------------
+ * Replaces: one iteration of LightGCN.propagate, scripts/train_lightgcn.py:69-72
+ *   (A = torch.sparse_coo_tensor(...); out = torch.sparse.mm(A, out); acc = acc + out) and, on
+ *   the last hop, the layer mean acc / (K + 1) of :73; with the CSC view, their autograd.
+ * For every row i of a CSR (sched over its rowptr, col [n_edges], val [n_edges] per slot):
+ *   s_i     = sum over the slots k of row i, in slot order, of val[k] * src[col[k]]  (fp32 FMAs)
+ *   out[i]  = s_i                          when out  != NULL
+ *   accw[i] = (acc_in[i] + s_i) / div      when accw != NULL  (acc0 == NULL: acc_in = 0;
+ *                                          IEEE division, skipped when div == 1)
+ * src [n_src, channels] and acc_in [n_rows, channels] may each be two row segments: rows
+ * [0, split) at the first pointer, the rest at the second (second NULL: one segment), so hop 1
+ * reads E_user.weight and E_item.weight where they are.  accw may be acc_in's buffer (in
+ * place); out and accw must not be the gathered table.  channels in {64, 128, 256}
+ * (ppgat_lgcn_supported).  workspace: the hub pieces' partial rows, added in piece order.
+ * Atomic-free: two launches give the same bits.  A K-hop propagate is K calls: hop 1 with
+ * acc_in = x0 writing out_1 and acc, middle hops updating acc in place, hop K writing only the
+ * result with div = K + 1.  The gradient with respect to x0 is the same K calls over the CSC
+ * view (bwd schedule, row, val_t = val[csc2csr]) applied to the incoming gradient. */
+int ppgat_lgcn_supported(int channels);
+int ppgat_lgcn_hop_workspace_bytes(int64_t n_hub_items, int channels, size_t* bytes);
+int ppgat_lgcn_hop(const ppgat_schedule* sched, const int32_t* col, const float* val, int64_t n_rows, int64_t n_src,
+                   int64_t n_edges, int channels, const float* src0, const float* src1, int64_t src_split,
+                   const float* acc0, const float* acc1, int64_t acc_split, float div, float* out, float* accw,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- sampled-evaluation candidates ---------------------------------------------------
  * Replaces: the candidate draw of eval_sampled, scripts/train_gat_pyg.py:157-167 (a Python
  *   loop over ~192k users: np.random.randint(0, n_items) redrawn while the item is in the

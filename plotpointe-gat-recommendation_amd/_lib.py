@@ -100,6 +100,12 @@ SIGNATURES = {
     "ppgat_bpr_sampler_workspace_bytes": (c_int, [c_i64, c_i64, ctypes.POINTER(c_sz)]),
     "ppgat_bpr_sampler_prepare": (c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "ppgat_bpr_sample": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_u64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "ppgat_bpr_sample_positives": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_u64, c_i64, c_vp,
+                                           c_vp, c_vp, c_vp, c_vp]),
+    "ppgat_lgcn_supported": (c_int, [c_int]),
+    "ppgat_lgcn_hop_workspace_bytes": (c_int, [c_i64, c_int, ctypes.POINTER(c_sz)]),
+    "ppgat_lgcn_hop": (c_int, [SP, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_f,
+                               c_vp, c_vp, c_vp, c_sz, c_vp]),
     "ppgat_eval_sample": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_u64, c_vp, c_vp, c_vp]),
     "ppgat_sampled_rank": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "ppgat_serve_topk_workspace_bytes": (c_int, [c_i64, c_int, c_int, ctypes.POINTER(c_sz)]),

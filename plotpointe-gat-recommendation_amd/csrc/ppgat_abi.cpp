@@ -865,6 +865,73 @@ int ppgat_bpr_sample(const int64_t* user_ptr, const int32_t* items_sorted, const
   return PPGAT_OK;
 }
 
+int ppgat_bpr_sample_positives(const int64_t* user_ptr, const int32_t* user_items, const int32_t* items_sorted,
+                               int64_t n_users, int64_t nnz, int64_t n_items, int64_t neg_per_pos, int64_t n_triples,
+                               uint64_t seed, int64_t t0, int64_t* u, int64_t* i, int64_t* j, int32_t* bad,
+                               void* stream) {
+  if (n_users < 0 || nnz < 0 || n_items < 0 || n_items > INT32_MAX || neg_per_pos < 1 || n_triples < 0 || t0 < 0)
+    return fail(PPGAT_ERR_INVALID, "bpr_sample_positives: bad sizes");
+  if (neg_per_pos > INT32_MAX || nnz > UINT32_MAX || t0 > nnz * neg_per_pos || n_triples > nnz * neg_per_pos - t0)
+    return fail(PPGAT_ERR_INVALID, "bpr_sample_positives: t0 + n_triples exceeds nnz * neg_per_pos");
+  if (!bad || (n_triples > 0 && (!user_ptr || !user_items || !items_sorted || !u || !i || !j || n_items < 1)))
+    return fail(PPGAT_ERR_INVALID, "bpr_sample_positives: null pointer");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (n_triples > 0) {
+    if (int rc = debug_range(user_items, 4, nnz, 0, n_items, "bpr_sample_positives: user_items", st)) return rc;
+    if (int rc = debug_range(user_ptr, 8, n_users + 1, 0, nnz + 1, "bpr_sample_positives: user_ptr", st)) return rc;
+  }
+  Timed t(PPGAT_K_SAMPLE, st);
+  hipError_t e = ppgat::bpr_sample_positives(user_ptr, user_items, items_sorted, n_users, n_items, neg_per_pos,
+                                             n_triples, seed, t0, u, i, j, bad, st);
+  if (e != hipSuccess) return hip_fail(e, "bpr_sample_positives");
+  return PPGAT_OK;
+}
+
+// ---- LightGCN propagation hop ---------------------------------------------------------
+int ppgat_lgcn_supported(int channels) { return ppgat::lgcn_channels_ok(channels) ? 1 : 0; }
+
+int ppgat_lgcn_hop_workspace_bytes(int64_t n_hub_items, int channels, size_t* bytes) {
+  if (!bytes || n_hub_items < 0) return fail(PPGAT_ERR_INVALID, "lgcn_hop_workspace_bytes: bad arguments");
+  if (!ppgat::lgcn_channels_ok(channels))
+    return fail(PPGAT_ERR_UNSUPPORTED, "lgcn_hop_workspace_bytes: channels must be 64, 128 or 256");
+  *bytes = ppgat::lgcn_workspace_bytes(n_hub_items, channels);
+  return PPGAT_OK;
+}
+
+int ppgat_lgcn_hop(const ppgat_schedule* sched, const int32_t* col, const float* val, int64_t n_rows, int64_t n_src,
+                   int64_t n_edges, int channels, const float* src0, const float* src1, int64_t src_split,
+                   const float* acc0, const float* acc1, int64_t acc_split, float div, float* out, float* accw,
+                   void* workspace, size_t workspace_bytes, void* stream) {
+  if (!ppgat::lgcn_channels_ok(channels)) return fail(PPGAT_ERR_UNSUPPORTED, "lgcn_hop: channels must be 64, 128 or 256");
+  if (n_rows < 0 || n_src < 0 || n_edges < 0) return fail(PPGAT_ERR_INVALID, "lgcn_hop: bad sizes");
+  if (n_rows >= (int64_t)1 << 31 || n_src >= (int64_t)1 << 31 || n_edges >= (int64_t)1 << 31)
+    return fail(PPGAT_ERR_UNSUPPORTED, "lgcn_hop: rows and edges must be < 2^31");
+  if (!(div > 0.f)) return fail(PPGAT_ERR_INVALID, "lgcn_hop: div must be > 0");
+  if (int rc = check_sched(sched, n_rows, "lgcn_hop")) return rc;
+  if ((src1 && (src_split < 0 || src_split > n_src)) || (acc0 && acc1 && (acc_split < 0 || acc_split > n_rows)))
+    return fail(PPGAT_ERR_INVALID, "lgcn_hop: split outside the table's rows");
+  if ((acc1 && !acc0) || (acc0 && !accw)) return fail(PPGAT_ERR_INVALID, "lgcn_hop: acc_in needs its first segment and accw");
+  if (!out && !accw) return fail(PPGAT_ERR_INVALID, "lgcn_hop: no output (out and accw are NULL)");
+  if (n_edges > 0 && (!col || !val || !src0)) return fail(PPGAT_ERR_INVALID, "lgcn_hop: null col, val or src");
+  if (out && (out == src0 || out == src1)) return fail(PPGAT_ERR_INVALID, "lgcn_hop: out must not be the gathered table");
+  if (accw && (accw == src0 || accw == src1))
+    return fail(PPGAT_ERR_INVALID, "lgcn_hop: accw must not be the gathered table");
+  if (sched->n_hub_items > 0 &&
+      (!workspace || workspace_bytes < ppgat::lgcn_workspace_bytes(sched->n_hub_items, channels)))
+    return fail(PPGAT_ERR_INVALID, "lgcn_hop: workspace too small for the hub pieces");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = debug_range(col, 4, n_edges, 0, n_src, "lgcn_hop: col", st)) return rc;
+  if (int rc = debug_range(sched->item_row, 4, sched->n_items, 0, n_rows, "lgcn_hop: item_row", st)) return rc;
+  if (int rc = debug_range(sched->item_end, 4, sched->n_items, 0, n_edges + 1, "lgcn_hop: item_end", st)) return rc;
+  const ppgat::ItemsArg it{sched->item_row, sched->item_beg, sched->item_end, sched->n_items, sched->n_hub_items,
+                           sched->n_long_items};
+  Timed t(PPGAT_K_FWD, st);
+  hipError_t e = ppgat::lgcn_hop(it, col, val, channels, src0, src1, src_split, acc0, acc1, acc_split, div, out, accw,
+                                 static_cast<float*>(workspace), sched->hub_row, sched->hub_ptr, sched->n_hubs, st);
+  if (e != hipSuccess) return hip_fail(e, "lgcn_hop");
+  return PPGAT_OK;
+}
+
 int ppgat_eval_sample(const int64_t* user_ptr, const int32_t* items_sorted, const int64_t* users, const int64_t* pos,
                       int64_t n_eval, int64_t n_neg, int64_t n_items, uint64_t seed, int64_t* cands, int32_t* bad,
                       void* stream) {

@@ -154,6 +154,18 @@ hipError_t bpr_sample(const int64_t* ptr, const int32_t* items_sorted, const int
                       const int64_t* n_eligible, int64_t n_items, int64_t S, uint64_t seed, int64_t t0, int64_t* u,
                       int64_t* i, int64_t* j, int32_t* bad, hipStream_t st);
 
+hipError_t bpr_sample_positives(const int64_t* ptr, const int32_t* items_orig, const int32_t* items_sorted,
+                                int64_t n_users, int64_t n_items, int64_t neg_per_pos, int64_t S, uint64_t seed,
+                                int64_t t0, int64_t* u, int64_t* i, int64_t* j, int32_t* bad, hipStream_t st);
+
+// LightGCN propagation hop (ppgat_lgcn.hip); src1 / acc1 == NULL: one segment
+bool lgcn_channels_ok(int C);
+size_t lgcn_workspace_bytes(int64_t n_hub_items, int C);
+hipError_t lgcn_hop(const ItemsArg& it, const int32_t* col, const float* val, int C, const float* src0,
+                    const float* src1, int64_t src_split, const float* acc0, const float* acc1, int64_t acc_split,
+                    float div, float* out, float* accw, float* partial, const int32_t* hub_row,
+                    const int32_t* hub_ptr, int64_t n_hubs, hipStream_t st);
+
 hipError_t eval_sample(const int64_t* ptr, const int32_t* items_sorted, const int64_t* users, const int64_t* pos,
                        int64_t n_eval, int64_t n_neg, int64_t n_items, uint64_t seed, int64_t* cands, int32_t* bad,
                        hipStream_t st);

@@ -83,6 +83,39 @@ __global__ void __launch_bounds__(256) k_bpr_sample(const int64_t* __restrict__ 
   u[s] = uu; i[s] = ii; j[s] = jj;
 }
 
+// Every positive x neg_per_pos (sample_bpr_batches, scripts/train_lightgcn.py:160-179): triple
+// t belongs to position p = t / neg_per_pos of user_items in the order given (users in order,
+// each user's items in list order -- the reference's enumeration), u = the owner of p (the
+// last user with ptr[u] <= p: users without items are stepped over), i = user_items[p], and
+// j = the first draw d = 0, 1, ... of the stream (seed, t, d) outside u's items.  One thread
+// per triple; the caller guarantees t0 + S <= nnz * neg_per_pos.
+__global__ void __launch_bounds__(256) k_bpr_sample_pos(const int64_t* __restrict__ ptr,
+                                                        const int32_t* __restrict__ items_orig,
+                                                        const int32_t* __restrict__ items,
+                                                        int64_t n_users, int64_t n_items, int64_t neg_per_pos,
+                                                        int64_t S, uint64_t seed, int64_t t0,
+                                                        int64_t* __restrict__ u, int64_t* __restrict__ i,
+                                                        int64_t* __restrict__ j, int32_t* __restrict__ bad) {
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= S) return;
+  const uint64_t t = (uint64_t)(t0 + s);
+  const int64_t p = (int64_t)(t / (uint64_t)neg_per_pos);
+  int64_t a = 0, b = n_users;  // first index in (0, n_users] whose ptr is > p, minus one
+  while (a < b) {
+    const int64_t mid = (a + b) >> 1;
+    if (ptr[mid + 1] > p) b = mid; else a = mid + 1;
+  }
+  const int64_t uu = a < n_users ? a : n_users - 1;
+  const int64_t lo = ptr[uu], hi = ptr[uu + 1];
+  int64_t jj = -1;
+  for (int d = 0; d < kMaxNegDraws; ++d) {
+    const int32_t c = (int32_t)below(draw64(seed, t, d), n_items);
+    if (!member(items, lo, hi, c)) { jj = c; break; }
+  }
+  if (jj < 0) { jj = 0; atomicOr(bad, 2); }
+  u[s] = uu; i[s] = items_orig[p]; j[s] = jj;
+}
+
 // Sampled-evaluation candidates (eval_sampled, scripts/train_gat_pyg.py:157-167): row b holds
 // the held-out positive, then n_neg negatives; negative k is the first draw d = 0, 1, ... of
 // the stream (seed, t = b * n_neg + k, d) that is neither one of the user's train items nor
@@ -163,6 +196,16 @@ hipError_t bpr_sample(const int64_t* ptr, const int32_t* items_sorted, const int
   if (err != hipSuccess || S <= 0) return err;
   hipLaunchKernelGGL(k_bpr_sample, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, ptr, items_sorted, eligible,
                      n_eligible, n_items, S, seed, t0, u, i, j, bad);
+  return hipGetLastError();
+}
+
+hipError_t bpr_sample_positives(const int64_t* ptr, const int32_t* items_orig, const int32_t* items_sorted,
+                                int64_t n_users, int64_t n_items, int64_t neg_per_pos, int64_t S, uint64_t seed,
+                                int64_t t0, int64_t* u, int64_t* i, int64_t* j, int32_t* bad, hipStream_t st) {
+  hipError_t err = hipMemsetAsync(bad, 0, sizeof(int32_t), st);
+  if (err != hipSuccess || S <= 0) return err;
+  hipLaunchKernelGGL(k_bpr_sample_pos, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, ptr, items_orig,
+                     items_sorted, n_users, n_items, neg_per_pos, S, seed, t0, u, i, j, bad);
   return hipGetLastError();
 }
 

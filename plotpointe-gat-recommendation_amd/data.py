@@ -217,6 +217,29 @@ def sample_bpr_epoch(train_pos_idx: Dict[int, np.ndarray], n_items: int, samples
     return np.array(out_u), np.array(out_i), np.array(out_j)
 
 
+def sample_lightgcn_batches(train_pos_idx: Dict[int, np.ndarray], n_items: int, neg_per_pos: int, batch_size: int):
+    """scripts/train_lightgcn.py:160-179 -- every train interaction (users in dict order, items
+    in list order) x ``neg_per_pos`` negatives, yielded every ``batch_size`` triples, with the
+    same Python ``random`` draw sequence, so a seeded run yields the reference's exact batches.
+    The device counterpart is ``sampler.BPRSampler.sample_positives``."""
+    pos_sets = {u: set(pos) for u, pos in train_pos_idx.items()}
+    out_u, out_i, out_j = [], [], []
+    for u in list(train_pos_idx.keys()):
+        s = pos_sets[u]
+        for i in train_pos_idx[u]:
+            for _ in range(neg_per_pos):
+                while True:
+                    j = random.randrange(n_items)
+                    if j not in s:
+                        break
+                out_u.append(u); out_i.append(int(i)); out_j.append(j)
+                if len(out_u) >= batch_size:
+                    yield np.array(out_u), np.array(out_i), np.array(out_j)
+                    out_u, out_i, out_j = [], [], []
+    if out_u:
+        yield np.array(out_u), np.array(out_i), np.array(out_j)
+
+
 def sample_bpr_numpy(user_ptr: np.ndarray, user_items: np.ndarray, n_items: int, samples: int,
                      seed: int = 42):
     """Vectorised uniform BPR sampler over a CSR user->train-items table (same

@@ -37,6 +37,7 @@ class BPRSampler:
         self.device = dev
         if self.n_users < 0:
             raise ValueError("BPRSampler: user_ptr must have n_users + 1 entries")
+        self.items_orig = items  # the order given: sample_positives enumerates it
         self.items = torch.empty(max(self.nnz, 1), dtype=torch.int32, device=dev)
         self.eligible = torch.empty(max(self.n_users, 1), dtype=torch.int32, device=dev)
         self.n_eligible = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -68,6 +69,33 @@ class BPRSampler:
             if bad & 2:
                 raise ValueError("BPRSampler: a user holds (almost) every item; no negative found")
         return out[0], out[1], out[2]
+
+    def sample_positives(self, neg_per_pos: int, batch_size: int, batch: int, seed: int = 42, check: bool = True):
+        """Mini-batch ``batch`` of an epoch of sample_bpr_batches (scripts/train_lightgcn.py:160-179)
+        -> (u, i, j) int64 [S]: every train interaction in the order given (users in order, each
+        user's items in list order) x ``neg_per_pos`` negatives, cut every ``batch_size`` triples
+        (the last batch is partial).  (u, i) equal the reference's batches exactly; j is the first
+        draw of the counter stream (seed, triple index, d) outside the user's items
+        (``ppgat_bpr_sample_positives``)."""
+        lib = _lib.load()
+        npp, bs, b = int(neg_per_pos), int(batch_size), int(batch)
+        total = self.nnz * npp
+        if npp < 1 or bs < 1 or b < 0 or b * bs >= max(total, 1):
+            raise ValueError(f"sample_positives: batch {b} of {self.n_batches(npp, bs) if npp > 0 and bs > 0 else 0}")
+        t0 = b * bs
+        S = min(bs, total - t0)
+        out = torch.empty(3, S, dtype=torch.int64, device=self.device)
+        _lib.check(lib.ppgat_bpr_sample_positives(self.ptr.data_ptr(), self.items_orig.data_ptr(),
+                                                  self.items.data_ptr(), self.n_users, self.nnz, self.n_items, npp,
+                                                  S, int(seed) & 0xFFFFFFFFFFFFFFFF, t0, out[0].data_ptr(),
+                                                  out[1].data_ptr(), out[2].data_ptr(), self._bad.data_ptr(),
+                                                  _lib.stream_handle(self.device)), "bpr_sample_positives")
+        if check and int(self._bad.item()) & 2:
+            raise ValueError("BPRSampler: a user holds (almost) every item; no negative found")
+        return out[0], out[1], out[2]
+
+    def n_batches(self, neg_per_pos: int, batch_size: int) -> int:
+        return -(-(self.nnz * int(neg_per_pos)) // int(batch_size))
 
     def eval_candidates(self, users, pos, n_neg: int, seed: int = 0, check: bool = True) -> torch.Tensor:
         """eval_sampled's candidates (train_gat_pyg.py:157-167) on the device: [B, n_neg + 1]

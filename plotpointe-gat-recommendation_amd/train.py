@@ -8,6 +8,8 @@ GCS is out of scope: the ``--*-prefix`` flags name LOCAL directories holding the
 names (interactions.parquet, node_maps.json, {fused,txt}_interacted.npy); outputs go to
 ``{models_prefix}/checkpoints/{run_id}.pt`` and ``{models_prefix}/metrics_{run_id}.json``.
 ``--synthetic cfg1|cfg2`` builds the SURVEY.md 8(d) stand-in inputs instead.
+``--model-family lightgcn`` is scripts/train_lightgcn.py's main(): its flags and defaults, the
+mini-batch loop over every train interaction x ``--neg-per-pos`` negatives, the same outputs.
 
     python -m plotpointe_gat_amd.train ...   (or: python plotpointe-gat-recommendation_amd/train.py ...)
 """
@@ -31,11 +33,13 @@ if __package__ in (None, ""):  # executed as a file
     sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
     _pkg = importlib.import_module("plotpointe-gat-recommendation_amd")
     data, evaluation, model_mod = _pkg.data, importlib.import_module(_pkg.__name__ + ".evaluation"), _pkg.model
-    sampler_mod = _pkg.sampler
+    sampler_mod, lightgcn_mod, optim_mod = _pkg.sampler, _pkg.lightgcn, _pkg.optim
 else:
     from . import data, evaluation
     from . import model as model_mod
     from . import sampler as sampler_mod
+    from . import lightgcn as lightgcn_mod
+    from . import optim as optim_mod
 
 
 def set_seed(seed: int):
@@ -93,6 +97,25 @@ class Config:
     item_features: str = "fused"
     loss: str = "bpr"
     model_family: str = "gat_pyg"
+
+
+@dataclass
+class LGCNConfig:
+    """train_lightgcn.py:33-48."""
+    project_id: str
+    region: str
+    staging_prefix: str
+    graphs_prefix: str
+    models_prefix: str
+    embed_dim: int = 64
+    n_layers: int = 3
+    lr: float = 1e-3
+    l2: float = 1e-4
+    epochs: int = 50
+    batch_size: int = 8192
+    neg_per_pos: int = 5
+    seed: int = 42
+    eval_neg_k: int = 1000
 
 
 def _local(prefix: str) -> Path:
@@ -157,6 +180,96 @@ def epoch_step(model, opt, item_feats, edge_index, n_users: int, u, i, j, loss: 
     return lo
 
 
+def user_csr(train_pos_idx: Dict[int, np.ndarray], n_users: int):
+    """(ptr [n_users + 1], items) over the train lists in user order, each list in its own order."""
+    lens = np.array([len(train_pos_idx.get(uu, ())) for uu in range(n_users)], dtype=np.int64)
+    ptr = np.concatenate([[0], np.cumsum(lens)])
+    flat = np.concatenate([np.asarray(train_pos_idx[uu], dtype=np.int64) for uu in range(n_users) if lens[uu]] or
+                          [np.zeros(0, dtype=np.int64)])
+    return ptr, flat
+
+
+def main_lightgcn(args):
+    """train_lightgcn.py main(): the mini-batch loop over every positive x neg_per_pos
+    (:313-336), sampled evaluation each epoch, best-val checkpoint on ndcg@20, reload, test."""
+    cfg = LGCNConfig(project_id=args.project_id, region=args.region, staging_prefix=args.staging_prefix,
+                     graphs_prefix=args.graphs_prefix, models_prefix=args.models_prefix, embed_dim=args.embed_dim,
+                     n_layers=3 if args.layers is None else args.layers, lr=1e-3 if args.lr is None else args.lr,
+                     l2=1e-4 if args.l2 is None else args.l2, epochs=50 if args.epochs is None else args.epochs,
+                     batch_size=args.batch_size, neg_per_pos=args.neg_per_pos, seed=args.seed,
+                     eval_neg_k=args.eval_neg_k)
+    if args.world_size > 1:
+        raise NotImplementedError("--model-family lightgcn runs on one GPU")
+    if args.deterministic:
+        enable_determinism(cfg.seed)
+    set_seed(cfg.seed)
+    if not torch.cuda.is_available():
+        raise RuntimeError("this trainer runs the HIP kernels: a ROCm GPU is required")
+    device = torch.device("cuda")
+    run_id = f"lgcn_d{cfg.embed_dim}_{int(time.time())}"
+    if args.structured_logs:
+        log_event("run_start", run_id=run_id, model_family="lightgcn", config={**cfg.__dict__, "device": str(device)})
+    gat_cfg = Config(project_id=args.project_id, region=args.region, staging_prefix=args.staging_prefix,
+                     graphs_prefix=args.graphs_prefix, embeddings_prefix=args.embeddings_prefix,
+                     models_prefix=args.models_prefix, item_features=args.item_features)
+    tr, va, te, n_users, n_items, _ = load_inputs(gat_cfg, args.synthetic)
+    # the adjacency and --exact-sampler follow the dict's own order, as the reference does; the device
+    # sampler enumerates users ascending (the same enumeration whenever the dict is in user order)
+    print(f"[LGCN] n_users={n_users}, n_items={n_items}")
+    adj_idx, adj_vals = lightgcn_mod.build_adj(n_users, n_items, tr)
+    model = lightgcn_mod.LightGCN(n_users, n_items, cfg.embed_dim, adj_idx, adj_vals, n_layers=cfg.n_layers).to(device)
+    opt = optim_mod.Adam(model.parameters(), lr=cfg.lr, weight_decay=cfg.l2)
+    out_dir = _local(cfg.models_prefix)
+    (out_dir / "checkpoints").mkdir(parents=True, exist_ok=True)
+    best_path = out_dir / "checkpoints" / f"{run_id}.pt"
+    metrics_path = out_dir / f"metrics_{run_id}.json"
+    best = -1.0
+    val_metrics: Dict[str, float] = {}
+    ptr, flat = user_csr(tr, n_users)
+    dev_sampler = sampler_mod.BPRSampler(ptr, flat, n_items, device=device)
+    n_batches = dev_sampler.n_batches(cfg.neg_per_pos, cfg.batch_size)
+    for epoch in range(1, cfg.epochs + 1):
+        model.train()
+        total = torch.zeros((), dtype=torch.float32, device=device)
+        if args.exact_sampler:
+            batches = (tuple(torch.from_numpy(a).long().to(device) for a in b)
+                       for b in data.sample_lightgcn_batches(tr, n_items, cfg.neg_per_pos, cfg.batch_size))
+        else:
+            batches = (dev_sampler.sample_positives(cfg.neg_per_pos, cfg.batch_size, b, seed=cfg.seed + epoch,
+                                                    check=False) for b in range(n_batches))
+        nb = 0
+        for u, i, j in batches:
+            total += lightgcn_mod.train_step(model, opt, u, i, j).detach()
+            nb += 1
+        avg_loss = float(total.item()) / max(1, nb)
+        print(f"[LGCN][Epoch {epoch}] train_bpr_loss={avg_loss:.4f}")
+        model.eval()
+        val_metrics = evaluation.eval_sampled(model, cfg, None, None, tr, va, fast=args.fast_eval,
+                                              sampler=dev_sampler if args.device_eval else None, seed=cfg.seed + epoch)
+        print(f"[LGCN][Epoch {epoch}] val: {val_metrics}")
+        if args.structured_logs:
+            log_event("epoch_end", run_id=run_id, epoch=epoch, loss=avg_loss, val=val_metrics)
+        if val_metrics.get("ndcg@20", 0.0) > best:
+            best = val_metrics.get("ndcg@20", 0.0)
+            torch.save({"state_dict": model.state_dict(), "config": cfg.__dict__}, best_path)
+            print("[LGCN] Saved new best checkpoint")
+    ckpt = torch.load(best_path, map_location=device, weights_only=True)
+    model.load_state_dict(ckpt["state_dict"])
+    model.eval()
+    test_metrics = evaluation.eval_sampled(model, cfg, None, None, tr, te, fast=args.fast_eval,
+                                           sampler=dev_sampler if args.device_eval else None, seed=cfg.seed)
+    print(f"[LGCN] test: {test_metrics}")
+    out = {"best_val_ndcg@20": float(best), "val": val_metrics, "test": test_metrics, "config": cfg.__dict__,
+           "notes": "Evaluation uses sampled 1000 negatives/user."}
+    with open(metrics_path, "w") as f:
+        json.dump(out, f, indent=2)
+    print(f"[LGCN] Complete. Wrote {best_path} and {metrics_path}")
+    if args.structured_logs:
+        log_event("run_complete", run_id=run_id, best_val_ndcg20=float(best), test=test_metrics,
+                  artifacts={"checkpoint": str(best_path), "metrics": str(metrics_path)})
+    return out
+
+
 class _GlobalRows(torch.nn.Module):
     """A row-sharded model seen as the single-GPU one by eval_sampled / export: forward returns
     every node's rows on every rank (an all_gather; evaluation only, not the training path)."""
@@ -194,12 +307,20 @@ def main(argv=None):
     ap.add_argument("--graphs-prefix", default="data/graphs")
     ap.add_argument("--embeddings-prefix", default="data/embeddings")
     ap.add_argument("--models-prefix", default="models/gat")
-    ap.add_argument("--model-family", choices=["gat_pyg", "gat_custom"], default="gat_pyg")
+    ap.add_argument("--model-family", choices=["gat_pyg", "gat_custom", "lightgcn"], default="gat_pyg")
     ap.add_argument("--hidden-dim", type=int, default=128)
-    ap.add_argument("--layers", type=int, default=2)
+    ap.add_argument("--layers", type=int, default=None, help="default 2 (GAT), 3 (lightgcn)")
     ap.add_argument("--heads", type=int, default=1)
     ap.add_argument("--attn-dropout", type=float, default=0.1)
-    ap.add_argument("--epochs", type=int, default=20)
+    ap.add_argument("--epochs", type=int, default=None, help="default 20 (GAT), 50 (lightgcn)")
+    ap.add_argument("--lr", type=float, default=None, help="default 1e-3")
+    ap.add_argument("--l2", type=float, default=None, help="Adam weight decay, default 1e-4")
+    ap.add_argument("--embed-dim", type=int, default=64, help="lightgcn: embedding width (64, 128 or 256)")
+    ap.add_argument("--batch-size", type=int, default=8192, help="lightgcn: triples per mini-batch")
+    ap.add_argument("--neg-per-pos", type=int, default=5, help="lightgcn: negatives per train interaction")
+    ap.add_argument("--exact-sampler", action="store_true",
+                    help="lightgcn: the reference's Python random stream (data.sample_lightgcn_batches) instead "
+                         "of the device sampler")
     ap.add_argument("--samples-per-epoch", type=int, default=200_000)
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--eval-neg-k", type=int, default=1000)
@@ -220,12 +341,20 @@ def main(argv=None):
     ap.add_argument("--partition", choices=["auto", "replicated", "halo"], default="auto",
                     help="auto: users sharded / items replicated for U-I graphs, halo otherwise")
     args = ap.parse_args(argv)
+    if args.model_family == "lightgcn":
+        return main_lightgcn(args)
+    args.layers = 2 if args.layers is None else args.layers
+    args.epochs = 20 if args.epochs is None else args.epochs
     cfg = Config(project_id=args.project_id, region=args.region, staging_prefix=args.staging_prefix,
                  graphs_prefix=args.graphs_prefix, embeddings_prefix=args.embeddings_prefix,
                  models_prefix=args.models_prefix, hidden_dim=args.hidden_dim, layers=args.layers, heads=args.heads,
                  attn_dropout=args.attn_dropout, epochs=args.epochs, samples_per_epoch=args.samples_per_epoch,
                  seed=args.seed, eval_neg_k=args.eval_neg_k, item_features=args.item_features, loss=args.loss,
                  model_family=args.model_family)
+    if args.lr is not None:
+        cfg.lr = args.lr
+    if args.l2 is not None:
+        cfg.l2 = args.l2
     if args.deterministic:
         enable_determinism(cfg.seed)
     set_seed(cfg.seed)
@@ -283,10 +412,7 @@ def main(argv=None):
     val_metrics: Dict[str, float] = {}
     dev_sampler = None
     if args.fast_sampler or args.device_eval:
-        lens = np.array([len(tr.get(uu, ())) for uu in range(n_users)], dtype=np.int64)
-        ptr = np.concatenate([[0], np.cumsum(lens)])
-        flat = np.concatenate([np.asarray(tr[uu], dtype=np.int64) for uu in range(n_users) if lens[uu]] or
-                              [np.zeros(0, dtype=np.int64)])
+        ptr, flat = user_csr(tr, n_users)
         dev_sampler = sampler_mod.BPRSampler(ptr, flat, n_items, device=device)
     for epoch in range(1, cfg.epochs + 1):
         model.train()
