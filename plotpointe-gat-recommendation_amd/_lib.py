@@ -17,7 +17,6 @@ c_int, c_i64, c_u64, c_f, c_vp, c_sz = (ctypes.c_int, ctypes.c_int64, ctypes.c_u
                                          ctypes.c_void_p, ctypes.c_size_t)
 
 
-
 class Schedule(ctypes.Structure):
     """include/ppgat.h ppgat_schedule"""
     _fields_ = [("item_row", c_vp), ("item_beg", c_vp), ("item_end", c_vp), ("n_items", c_i64),
@@ -222,6 +221,47 @@ def ptr(t) -> int:
     return None if t is None else t.data_ptr()
 
 
+def row_ptr(t, row: int = 0):
+    """(device address of t[row], row stride of t in elements); None -> (None, 0).
+
+    The offset comes from the tensor's own row stride and element size, never from a slice: an
+    empty slice t[n:] has a null data_ptr, while the kernels are handed base + n * rowbytes.
+    0 <= row <= t.size(0) (one past the end: a zero-row range), and the row itself must be
+    dense -- unit stride in the last dimension, no gaps between the inner ones -- so a column
+    view S[:, c:] is fine (ld is then its parent's width) and a transpose is not."""
+    if t is None:
+        return None, 0
+    if not 0 <= row <= t.size(0):
+        raise IndexError(f"row_ptr: row {row} outside [0, {t.size(0)}]")
+    if not t.is_contiguous():  # (the common case needs no look at the inner dimensions)
+        dense = 1
+        for d in range(t.dim() - 1, 0, -1):
+            if t.size(d) != 1 and t.stride(d) != dense:
+                raise ValueError(f"row_ptr: rows are not dense (shape {tuple(t.shape)}, strides {t.stride()})")
+            dense *= t.size(d)
+    return t.data_ptr() + row * t.stride(0) * t.element_size(), t.stride(0)
+
+
+def edge_ptrs(n_edges: int, *arrays):
+    """Device pointers of per-edge arrays: NULL for each when there are no edges (the arrays
+    may then be empty slices or placeholders)."""
+    return tuple(ptr(a) if n_edges else None for a in arrays)
+
+
+def seed64(seed) -> int:
+    """A Python int as the ABI's uint64 seed (two's complement of a negative one)."""
+    return int(seed) & (2**64 - 1)
+
+
+def workspace(entry, *args, device, floor: int = 0):
+    """(uint8 tensor, byte count) for the ``*_workspace_bytes`` entry called with ``args``; the
+    tensor holds max(count, floor) bytes, the count is what the launch is told."""
+    import torch
+    nbytes = ctypes.c_size_t(0)
+    check(entry(*args, ctypes.byref(nbytes)), entry.__name__)
+    return torch.empty(max(int(nbytes.value), floor), dtype=torch.uint8, device=device), nbytes.value
+
+
 def stream_handle(device) -> int:
     import torch
     return torch.cuda.current_stream(device).cuda_stream
@@ -279,4 +319,4 @@ def dropout_set_epoch(epoch: int, device=None):
     import torch
     lib = load()
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-    check(lib.ppgat_dropout_set_epoch(int(epoch) & (2**64 - 1), stream_handle(dev)), "dropout_set_epoch")
+    check(lib.ppgat_dropout_set_epoch(seed64(epoch), stream_handle(dev)), "dropout_set_epoch")

@@ -36,7 +36,6 @@ the ranks' own RNG states.
 """
 from __future__ import annotations
 
-import ctypes
 import os
 import weakref
 from dataclasses import dataclass
@@ -47,7 +46,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import _lib
+from . import _launch, _lib
 
 
 # ---------------------------------------------------------------------------
@@ -1178,12 +1177,10 @@ def _halo_xgat_backward(saved: dict, g: torch.Tensor, hg: "HaloGraph", comm: "Co
     This is the PPGAT_XGAT_GATHER=g variant; by default D is deferred instead
     (_halo_xgat_backward_deferred_d: no gt GEMM, D's partials go home and back out)."""
     from . import hip_ops as O
-    lib = _lib.load()
     x, W, A = saved["x"], saved["W"], saved["A"]
     s_src, s_dst, agg, m, inv_l = saved["s_src"], saved["s_dst"], saved["agg"], saved["m"], saved["inv_l"]
     H, C, K, slope, p, seed, has_bias = saved["meta"]
     dev = x.device
-    st = _lib.stream_handle(dev)
     n0, R, sv = hg.n_own, hg.R, hg.src_views
     E = sv.n_edges
     g = g.contiguous()
@@ -1195,12 +1192,10 @@ def _halo_xgat_backward(saved: dict, g: torch.Tensor, hg: "HaloGraph", comm: "Co
         gtab.start(cls, g)
     # 1. destination state of the own rows
     Wg = torch.empty(C, H * K, dtype=torch.float32, device=dev)
-    _lib.check(lib.ppgat_xgat_weights(W.data_ptr(), None, None, H, C, K, None, None, Wg.data_ptr(), st),
-               "xgat_weights")
+    _launch.xgat_weights(W, None, None, H, C, Wg=Wg)
     gt = O.gemm_nn(g, Wg, 0, H * K)
     nst = torch.empty(max(n0, 1), 4 * H, dtype=torch.float32, device=dev)
-    _lib.check(lib.ppgat_xgat_bwd_prologue(gt.data_ptr(), agg.data_ptr(), s_dst.data_ptr(), m.data_ptr(),
-                                           inv_l.data_ptr(), n0, K, H, nst.data_ptr(), st), "xgat_bwd_prologue")
+    _launch.xgat_bwd_prologue(gt, agg, s_dst, m, inv_l, n0, K, H, nst)
     del gt, Wg
     nst = nst[:n0]
     ntab = HaloRows(hg, comm, stages, 4 * H, nst)
@@ -1217,14 +1212,14 @@ def _halo_xgat_backward(saved: dict, g: torch.Tensor, hg: "HaloGraph", comm: "Co
     for _, sched, base, need in phases:
         for tab in (gtab, ntab):
             tab.wait_all() if need is None else tab.wait(need)
-        O._xgat_edges_bwd_g(lib, sched, sv, base, hs, s_src, ntab.x, gtab.x, acc, S, dz, H, C, slope, p, seed,
-                            saved["seed_buf"], st)
+        _launch.xgat_bwd_edges_g(sched, sv, base, hs, s_src, ntab.x, gtab.x, acc, S, dz, H, C, slope, p, seed,
+                                 saved["seed_buf"])
     gtab.wait_all()
     ntab.wait_all()
     del hs
     # 4. ds_dst: partial sums over the table rows, the halo rows' back to their owners
     dsd = torch.zeros(max(R, 1), H, dtype=torch.float32, device=dev)
-    O._xgat_dst_sum(lib, sv, dz, dsd, H, E, st, col0=0, ld=H)
+    O._xgat_dst_sum(sv, dz, dsd, H)
     del dz
     S = S[:n0]
     S[:, H:].copy_(_partials_home(hg, comm, stages, dsd))
@@ -1233,7 +1228,7 @@ def _halo_xgat_backward(saved: dict, g: torch.Tensor, hg: "HaloGraph", comm: "Co
         torch.zeros(0, K, dtype=torch.float32, device=dev)
     del acc
     # 6. weight gradients (the sums over ranks: the dense all-reduce)
-    return O._xgat_weight_grads(lib, saved, g, S, dx, want_bias_grad, st, x_rows=x[:n0],
+    return O._xgat_weight_grads(None, saved, g, S, dx, want_bias_grad, None, x_rows=x[:n0],
                                 xbits=_source_colmax_bits(x[:n0], hg, comm, saved))
 
 
@@ -1291,12 +1286,10 @@ def _bwd_tables(saved: dict, hg: "HaloGraph", comm: "Comm", stages, g_width: int
 def _ntab_make(saved: dict, hg: "HaloGraph", comm: "Comm", stages, dev) -> "HaloRows":
     """The softmax-state table {s_dst, m, inv_l, .} [R, 4H] of a multi-head halo layer, the own
     rows filled (straight into the table, no copy)."""
-    lib = _lib.load()
     s_dst, m, inv_l = saved["s_dst"], saved["m"], saved["inv_l"]
     H = saved["meta"][0]
     ntab = HaloRows(hg, comm, stages, 4 * H, s_dst)
-    _lib.check(lib.ppgat_xgat_nstate(s_dst.data_ptr(), m.data_ptr(), inv_l.data_ptr(), None, hg.n_own, H,
-                                     ntab.x.data_ptr(), _lib.stream_handle(dev)), "xgat_nstate")
+    _launch.xgat_nstate(s_dst, m, inv_l, None, hg.n_own, H, ntab.x)
     return ntab
 
 
@@ -1334,11 +1327,9 @@ def _halo_xgat_backward_deferred_d(saved: dict, g, hg: "HaloGraph", comm: "Comm"
     gradient is written straight into the layer below's g table and its exchanges start before
     this layer's weight gradients, so they run beside them."""
     from . import hip_ops as O
-    lib = _lib.load()
     x, W, A, s_src = saved["x"], saved["W"], saved["A"], saved["s_src"]
     H, C, K, slope, p, seed, has_bias = saved["meta"]
     dev = x.device
-    st = _lib.stream_handle(dev)
     n0, R, sv = hg.n_own, hg.R, hg.src_views
     E = sv.n_edges
     seed_buf = saved["seed_buf"]
@@ -1396,25 +1387,14 @@ def _halo_xgat_backward_deferred_d(saved: dict, g, hg: "HaloGraph", comm: "Comm"
             O.gemm_nn(x[r0:r1], W, 1, H * C, alpha=1.0 / H, out=hs[r0:r1])
         for tab in (gtab, ntab):
             tab.wait_all() if need is None else tab.wait(need)
-        nbytes = ctypes.c_size_t(0)
-        _lib.check(lib.ppgat_xgat_bwd_g_workspace_bytes(sched.n_hub_items, C, H, ctypes.byref(nbytes)), "xgat_g_ws")
-        ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev)
-        cs = sched.cstruct()
-        _lib.check(lib.ppgat_xgat_bwd_edges_gd_colmax(ctypes.byref(cs), _lib.ptr(sv.row) if E else None,
-                                                      _lib.ptr(sv.csc_eid) if E else None, None, E, C, H,
-                                                      hs.data_ptr() + 4 * base * H * C,
-                                                      s_src.data_ptr() + 4 * base * H, ntab.x.data_ptr(),
-                                                      gtab.x.data_ptr(), C, float(slope), float(p),
-                                                      int(seed) & (2**64 - 1), _lib.ptr(seed_buf),
-                                                      acc.data_ptr() + 4 * base * H * C, dz.data_ptr(),
-                                                      pdal.data_ptr(), gbits.data_ptr(), ws.data_ptr(), nbytes.value,
-                                                      st), "xgat_bwd_edges_gd_colmax")
+        _launch.xgat_bwd_edges_gd_colmax(sched, sv, base, hs, s_src, ntab.x, gtab.x, acc, dz, pdal, gbits, H, C, slope,
+                                         p, seed, seed_buf)
     gtab.wait_all()
     ntab.wait_all()
     del hs
     # D: per table row partial sums of beta dalpha, completed at the owner, sent back out
     Dp = torch.zeros(max(R, 1), H, dtype=torch.float32, device=dev)
-    O._xgat_dst_sum(lib, sv, pdal, Dp, H, E, st, col0=0, ld=H)
+    O._xgat_dst_sum(sv, pdal, Dp, H)
     del pdal
     Dtab = HaloRows(hg, comm, stages, H, Dp)
     Dtab.x[:n0].copy_(_partials_home(hg, comm, stages, Dp))
@@ -1423,24 +1403,15 @@ def _halo_xgat_backward_deferred_d(saved: dict, g, hg: "HaloGraph", comm: "Comm"
         Dtab.start(cls, Dtab.x[:n0])
     Dtab.wait_all()
     Dx = Dtab.x.contiguous()  # nstate {s_dst, m, inv_l, D} of every table row
-    _lib.check(lib.ppgat_xgat_nstate_set_d(ntab.x.data_ptr(), Dx.data_ptr(), R, H, st), "xgat_nstate_set_d")
+    _launch.xgat_nstate_set_d(ntab.x, Dx, R, H)
     del Dtab
     # dz in place over dalpha, ds_src per own source
     S = torch.zeros(max(n0, 1), 2 * H, dtype=torch.float32, device=dev)
     for sched, base, _ in phases:
-        nbytes = ctypes.c_size_t(0)
-        _lib.check(lib.ppgat_xgat_bwd_dz_workspace_bytes(sched.n_hub_items, H, ctypes.byref(nbytes)), "xgat_dz_ws")
-        ws = torch.empty(max(int(nbytes.value), 4), dtype=torch.uint8, device=dev)
-        cs = sched.cstruct()
-        _lib.check(lib.ppgat_xgat_bwd_dz(ctypes.byref(cs), _lib.ptr(sv.row) if E else None,
-                                         _lib.ptr(sv.csc_eid) if E else None, None, E, H,
-                                         s_src.data_ptr() + 4 * base * H, ntab.x.data_ptr(), float(slope), float(p),
-                                         int(seed) & (2**64 - 1), _lib.ptr(seed_buf), dz.data_ptr(),
-                                         S.data_ptr() + 4 * base * 2 * H, 2 * H, ws.data_ptr(), nbytes.value, st),
-                   "xgat_bwd_dz")
+        _launch.xgat_bwd_dz(sched, sv, base, s_src, ntab.x, dz, S, H, slope, p, seed, seed_buf)
     # ds_dst: partials per table row, completed at the owner
     dsd = torch.zeros(max(R, 1), H, dtype=torch.float32, device=dev)
-    O._xgat_dst_sum(lib, sv, dz, dsd, H, E, st, col0=0, ld=H)
+    O._xgat_dst_sum(sv, dz, dsd, H)
     del dz
     S = S[:n0]
     S[:, H:].copy_(_partials_home(hg, comm, stages, dsd))
@@ -1486,7 +1457,8 @@ def _halo_xgat_backward_deferred_d(saved: dict, g, hg: "HaloGraph", comm: "Comm"
         dx = O.gemm_nn(acc[:n0], W, 0, K, alpha=1.0 / H, rank=(S, A.view(2 * H, K))) if n0 else \
             torch.zeros(0, K, dtype=torch.float32, device=dev)
     del acc
-    return O._xgat_weight_grads(lib, saved, g, S, dx, want_bias_grad, st, x_rows=x[:n0], xbits=xbits, gbits=gbits)
+    return O._xgat_weight_grads(None, saved, g, S, dx, want_bias_grad, None, x_rows=x[:n0], xbits=xbits,
+                                gbits=gbits)
 
 
 class _ShardedBase(torch.nn.Module):
@@ -1982,22 +1954,17 @@ class RepHooks:
     def merge_fwd(self, out, m, inv_l, agg, bias, heads: int, C: int):
         if not self.comm.active:
             return
-        lib = _lib.load()
         rg, RU = self.rg, self.RU
         n = rg.n_items
         dev = out.device
         mx = torch.empty(n, heads, dtype=torch.float32, device=dev)
         pack = torch.empty(n * heads * (C + 1), dtype=torch.float32, device=dev)
-        rp = rg.view.rowptr[RU:]
-        args = (rp.data_ptr(), n, heads, C, out.data_ptr() + 4 * RU * C,
-                agg.data_ptr() + 4 * RU * heads * C if agg is not None else None, _lib.ptr(bias),
-                m.data_ptr() + 4 * RU * heads, inv_l.data_ptr() + 4 * RU * heads, mx.data_ptr(), pack.data_ptr(),
-                _lib.stream_handle(dev))
-        _lib.check(lib.ppgat_rep_merge(0, *args), "rep_merge")
+        args = (rg.view.rowptr, RU, n, heads, C, out, agg, bias, m, inv_l, mx, pack)
+        _launch.rep_merge(0, *args)
         self.comm.all_reduce_(mx, dist.ReduceOp.MAX)
-        _lib.check(lib.ppgat_rep_merge(1, *args), "rep_merge")
+        _launch.rep_merge(1, *args)
         self.comm.all_reduce_(pack)
-        _lib.check(lib.ppgat_rep_merge(2, *args), "rep_merge")
+        _launch.rep_merge(2, *args)
 
     def merge_fwd_async(self, out, m, inv_l, agg, bias, heads: int, C: int):
         """merge_fwd on the communication stream, after the main stream's work so far (the

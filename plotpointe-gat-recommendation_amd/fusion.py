@@ -144,7 +144,7 @@ def relu_dropout(z: torch.Tensor, p: float, seed: int, grad: Optional[torch.Tens
     out = torch.empty_like(z) if grad is None else grad
     if grad is not None and (grad.shape != z.shape or not grad.is_contiguous()):
         raise ValueError("relu_dropout: grad must be contiguous and shaped like z")
-    _lib.check(lib.ppgat_relu_dropout(z.data_ptr(), z.numel(), float(p), int(seed) & (2**64 - 1),
+    _lib.check(lib.ppgat_relu_dropout(z.data_ptr(), z.numel(), float(p), _lib.seed64(seed),
                                       0 if grad is None else 1, out.data_ptr(), _lib.stream_handle(z.device)),
                "relu_dropout")
     return out

@@ -15,7 +15,7 @@ from typing import Callable, Optional
 
 import torch
 
-from . import _lib
+from . import _launch, _lib
 
 
 def _require(cond: bool, msg: str):
@@ -84,12 +84,10 @@ def schedule_build(ptr: torch.Tensor, n_edges: int, max_edges: int = MAX_EDGES_P
     hub_row = torch.empty(max(N, 1), **i32)
     hub_ptr = torch.empty(N + 1, **i32)
     counts = torch.empty(4, **i32)
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(lib.ppgat_schedule_workspace_bytes(N, ctypes.byref(nbytes)), "schedule_workspace_bytes")
-    ws = torch.empty(max(int(nbytes.value), 1), dtype=torch.uint8, device=dev)
+    ws, nbytes = _lib.workspace(lib.ppgat_schedule_workspace_bytes, N, device=dev, floor=1)
     _lib.check(lib.ppgat_schedule_build(ptr.data_ptr(), N, n_edges, max_edges, item_row.data_ptr(),
                                         item_beg.data_ptr(), item_end.data_ptr(), hub_row.data_ptr(),
-                                        hub_ptr.data_ptr(), counts.data_ptr(), ws.data_ptr(), nbytes.value,
+                                        hub_ptr.data_ptr(), counts.data_ptr(), ws.data_ptr(), nbytes,
                                         _lib.stream_handle(dev)), "schedule_build")
     n_hubs, n_hub_items, n_items, n_long_rows = (int(v) for v in counts.cpu().tolist())
     return Schedule(item_row, item_beg, item_end, hub_row, hub_ptr, n_items, n_hub_items, n_hubs, max_edges,
@@ -156,13 +154,11 @@ def csr_build(edge_index: torch.Tensor, n_nodes: int, max_edges: int = MAX_EDGES
     csc_eid = torch.empty(max(E, 1), **i32)
     csc2csr = torch.empty(max(E, 1), **i32)
     bad = torch.empty(1, **i32)
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(lib.ppgat_csr_workspace_bytes(N, E, ctypes.byref(nbytes)), "csr_workspace_bytes")
-    ws = torch.empty(max(int(nbytes.value), 1), dtype=torch.uint8, device=dev)
+    ws, nbytes = _lib.workspace(lib.ppgat_csr_workspace_bytes, N, E, device=dev, floor=1)
     with torch.cuda.device(dev):
         _lib.check(lib.ppgat_csr_build(ei.data_ptr(), E, N, rowptr.data_ptr(), col.data_ptr(), csr_eid.data_ptr(),
                                        colptr.data_ptr(), row.data_ptr(), csc_eid.data_ptr(), csc2csr.data_ptr(),
-                                       bad.data_ptr(), ws.data_ptr(), nbytes.value, _lib.stream_handle(dev)),
+                                       bad.data_ptr(), ws.data_ptr(), nbytes, _lib.stream_handle(dev)),
                    "csr_build")
     nbad = int(bad.item())
     if nbad:
@@ -183,7 +179,7 @@ def _csr2csc(g) -> torch.Tensor:
     if g.csr2csc is None:
         E = g.n_edges
         inv = torch.empty(max(E, 1), dtype=torch.int32, device=g.csc2csr.device)
-        _lib.check(_lib.load().ppgat_invert_index(_lib.ptr(g.csc2csr) if E else None, E, inv.data_ptr(),
+        _lib.check(_lib.load().ppgat_invert_index(*_lib.edge_ptrs(E, g.csc2csr), E, inv.data_ptr(),
                                                   _lib.stream_handle(inv.device)), "invert_index")
         g.csr2csc = inv[:E]
     return g.csr2csc
@@ -229,7 +225,6 @@ graph_cache = _GraphCache()
 # node scores / fused forward / fused backward
 # ---------------------------------------------------------------------------
 def node_scores(h: torch.Tensor, att_src: torch.Tensor, att_dst: torch.Tensor, heads: int, channels: int):
-    lib = _lib.load()
     N = h.size(0)
     _check_dev("h", h, torch.float32)
     _check_dev("att_src", att_src, torch.float32, h.device)
@@ -238,9 +233,7 @@ def node_scores(h: torch.Tensor, att_src: torch.Tensor, att_dst: torch.Tensor, h
     _require(att_src.numel() == heads * channels and att_dst.numel() == heads * channels, "att must be [H, C]")
     s_src = torch.empty(N, heads, dtype=torch.float32, device=h.device)
     s_dst = torch.empty(N, heads, dtype=torch.float32, device=h.device)
-    _lib.check(lib.ppgat_node_scores(h.data_ptr(), att_src.data_ptr(), att_dst.data_ptr(), N, heads, channels,
-                                     s_src.data_ptr(), s_dst.data_ptr(), _lib.stream_handle(h.device)),
-               "node_scores")
+    _launch.node_scores(h, att_src, att_dst, heads, channels, s_src, s_dst)
     return s_src, s_dst
 
 
@@ -304,22 +297,8 @@ def _fwd_rows(g: CSRGraph, sched: Schedule, r0: int, n: int, h, s_src, s_dst, bi
               mode: int, slope: float, dropout_p: float, seed: int, seed_buf, out, m, inv_l, agg):
     """The forward over the destination rows [r0, r0 + n) of ``sched`` (row ids relative to
     r0; edge slots and source rows absolute): destination-indexed pointers are offset by r0."""
-    lib = _lib.load()
-    dev = h.device
-    HC = heads * channels
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(lib.ppgat_fwd_workspace_bytes(sched.n_hub_items, heads, channels, ctypes.byref(nbytes)),
-               "fwd_workspace_bytes")
-    ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev)
-    cs = sched.cstruct()
-    _lib.check(lib.ppgat_fwd(ctypes.byref(cs), _lib.ptr(g.col) if g.n_edges else None,
-                             _lib.ptr(g.csr_eid) if g.n_edges else None, n, g.n_edges, heads, channels,
-                             h.data_ptr(), s_src.data_ptr(), s_dst.data_ptr() + 4 * r0 * heads, _lib.ptr(bias), mode,
-                             float(slope), float(dropout_p), int(seed) & (2**64 - 1), _lib.ptr(seed_buf),
-                             out.data_ptr() + 4 * r0 * channels, m.data_ptr() + 4 * r0 * heads,
-                             inv_l.data_ptr() + 4 * r0 * heads,
-                             agg.data_ptr() + 4 * r0 * HC if agg is not None else None, ws.data_ptr(), nbytes.value,
-                             _lib.stream_handle(dev)), "gat_fwd")
+    _launch.fwd(sched, g.col, g.csr_eid, g.n_edges, r0, n, h, s_src, s_dst, bias, heads, channels, mode, slope,
+                dropout_p, seed, seed_buf, out, m, inv_l, agg)
 
 
 def gat_bwd(g: CSRGraph, h, s_src, s_dst, att_src, att_dst, bias, out, agg, m, inv_l, grad_out, heads: int,
@@ -333,21 +312,16 @@ def gat_bwd(g: CSRGraph, h, s_src, s_dst, att_src, att_dst, bias, out, agg, m, i
     datt_src = torch.empty(heads, channels, dtype=torch.float32, device=dev)
     datt_dst = torch.empty(heads, channels, dtype=torch.float32, device=dev)
     dbias = torch.empty(channels, dtype=torch.float32, device=dev) if want_bias_grad else None
-    nbytes = ctypes.c_size_t(0)
-    sched = g.bwd_sched
-    _lib.check(lib.ppgat_bwd_workspace_bytes(N, g.n_edges, sched.n_hub_items, heads, channels,
-                                             ctypes.byref(nbytes)), "bwd_workspace_bytes")
-    ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev)
-    E = g.n_edges
+    sched, E = g.bwd_sched, g.n_edges
+    ws, nbytes = _lib.workspace(lib.ppgat_bwd_workspace_bytes, N, E, sched.n_hub_items, heads, channels, device=dev)
     cs = sched.cstruct()
-    _lib.check(lib.ppgat_bwd(ctypes.byref(cs), g.rowptr.data_ptr(), _lib.ptr(g.row) if E else None,
-                             _lib.ptr(g.csc_eid) if E else None, _lib.ptr(g.csc2csr) if E else None, N, E, heads,
-                             channels, h.data_ptr(), s_src.data_ptr(), s_dst.data_ptr(), att_src.data_ptr(),
-                             att_dst.data_ptr(), _lib.ptr(bias), out.data_ptr(), _lib.ptr(agg), m.data_ptr(),
-                             inv_l.data_ptr(), grad_out.data_ptr(), mode, float(slope), float(dropout_p),
-                             int(seed) & (2**64 - 1), _lib.ptr(seed_buf), grad_h.data_ptr(), datt_src.data_ptr(),
-                             datt_dst.data_ptr(),
-                             _lib.ptr(dbias), ws.data_ptr(), nbytes.value, _lib.stream_handle(dev)), "gat_bwd")
+    _lib.check(lib.ppgat_bwd(ctypes.byref(cs), g.rowptr.data_ptr(), *_lib.edge_ptrs(E, g.row, g.csc_eid, g.csc2csr),
+                             N, E, heads, channels, h.data_ptr(), s_src.data_ptr(), s_dst.data_ptr(),
+                             att_src.data_ptr(), att_dst.data_ptr(), _lib.ptr(bias), out.data_ptr(), _lib.ptr(agg),
+                             m.data_ptr(), inv_l.data_ptr(), grad_out.data_ptr(), mode, float(slope),
+                             float(dropout_p), _lib.seed64(seed), _lib.ptr(seed_buf), grad_h.data_ptr(),
+                             datt_src.data_ptr(), datt_dst.data_ptr(), _lib.ptr(dbias), ws.data_ptr(), nbytes,
+                             _lib.stream_handle(dev)), "gat_bwd")
     return grad_h, datt_src, datt_dst, dbias
 
 
@@ -399,35 +373,13 @@ def _bwd_edges_src(g: CSRGraph, sched: Schedule, r0: int, h, s_src, nstate, grad
     """Pass B over the source rows of ``sched`` (row ids relative to r0; edge slots and
     destination rows absolute) into D, S[:, :H] and dz -- dz in CSC order (dz_slot NULL: one
     contiguous store per edge instead of a 4-B scatter to its CSR slot)."""
-    lib = _lib.load()
-    dev = h.device
-    E, HC = g.n_edges, heads * channels
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(lib.ppgat_fwd_workspace_bytes(sched.n_hub_items, heads, channels, ctypes.byref(nbytes)),
-               "workspace_bytes")
-    ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev)
-    cs = sched.cstruct()
-    st = _lib.stream_handle(dev)
-    _lib.check(lib.ppgat_bwd_edges(ctypes.byref(cs), _lib.ptr(g.row) if E else None,
-                                   _lib.ptr(g.csc_eid) if E else None, None, E, heads,
-                                   channels, h.data_ptr() + 4 * r0 * HC, s_src.data_ptr() + 4 * r0 * heads,
-                                   nstate.data_ptr(), grad_out.data_ptr(),
-                                   mode, float(slope), float(p), int(seed) & (2**64 - 1), _lib.ptr(seed_buf),
-                                   D.data_ptr() + 4 * r0 * HC, HC,
-                                   S.data_ptr() + 4 * r0 * 2 * heads, 2 * heads, dz.data_ptr(), ws.data_ptr(),
-                                   nbytes.value, st),
-               "bwd_edges")
+    _launch.bwd_edges(sched, g.row, g.csc_eid, None, g.n_edges, r0, h, s_src, nstate, grad_out, heads, channels, mode,
+                      slope, p, seed, seed_buf, D, S, dz)
 
 
 def _bwd_dst_sum(g: CSRGraph, dz, S, heads):
-    lib = _lib.load()
-    dev = dz.device
-    fs = g.fwd_sched.cstruct()
-    dws = torch.empty(max(g.fwd_sched.n_hub_items * heads, 1), dtype=torch.float32, device=dev)
-    E = g.n_edges
-    _lib.check(lib.ppgat_bwd_dst_sum_csc(ctypes.byref(fs), g.n_nodes, E, heads, dz.data_ptr(),
-                                         _lib.ptr(_csr2csc(g)) if E else None, S.data_ptr() + 4 * heads, 2 * heads,
-                                         dws.data_ptr(), dws.numel() * 4, _lib.stream_handle(dev)), "bwd_dst_sum_csc")
+    _launch.bwd_dst_sum(g.fwd_sched, g.n_nodes, g.n_edges, heads, dz, _csr2csc(g) if g.n_edges else None,
+                        S[:, heads:], csc=True)
 
 
 def _bwd_edges_dst(g: CSRGraph, h, s_src, nstate, grad_out, D, S, heads, channels, mode, slope, p, seed,
@@ -435,10 +387,7 @@ def _bwd_edges_dst(g: CSRGraph, h, s_src, nstate, grad_out, D, S, heads, channel
     """Pass B into D [N, HC] (dh_msg) and S[:, :H] (ds_src); the destination sum into
     S[:, H:2H] (ds_dst).  S [N, 2H] is compact (its scattered per-node writes stay in L2)
     and D keeps whole 512-B rows for the GEMMs that read it."""
-    lib = _lib.load()
-    dev = h.device
-    N, E, HC = g.n_nodes, g.n_edges, heads * channels
-    dz = torch.empty(max(E, 1) * heads, dtype=torch.float32, device=dev)
+    dz = torch.empty(max(g.n_edges, 1) * heads, dtype=torch.float32, device=h.device)
     _bwd_edges_src(g, g.bwd_sched, 0, h, s_src, nstate, grad_out, D, S, dz, heads, channels, mode, slope, p, seed,
                    seed_buf)
     _bwd_dst_sum(g, dz, S, heads)
@@ -689,15 +638,8 @@ class GATLayer(torch.autograd.Function):
         dbias = torch.empty(C, dtype=torch.float32, device=dev) if want_db else None
 
         def prologue(r0, r1, db):
-            n = r1 - r0
-            rows = int(lib.ppgat_bwd_partial_rows(n))
-            part = torch.empty(max(rows, 1) * C, dtype=torch.float32, device=dev) if db is not None else None
-            _lib.check(lib.ppgat_bwd_prologue(g_out.data_ptr() + 4 * r0 * C, out.data_ptr() + 4 * r0 * C,
-                                              agg.data_ptr() + 4 * r0 * HC if has_agg else None,
-                                              _lib.ptr(b) if has_bias else None, s_dst.data_ptr() + 4 * r0 * heads,
-                                              m.data_ptr() + 4 * r0 * heads, inv_l.data_ptr() + 4 * r0 * heads, n,
-                                              heads, C, mode, nstate.data_ptr() + 16 * r0 * heads, _lib.ptr(db),
-                                              _lib.ptr(part), _lib.stream_handle(dev)), "bwd_prologue")
+            _launch.bwd_prologue(r0, r1 - r0, g_out, out, agg if has_agg else None, b if has_bias else None, s_dst, m,
+                                 inv_l, heads, C, mode, nstate, db)
 
         D = torch.empty(N, HC, dtype=torch.float32, device=dev)
         S = torch.empty(N, 2 * heads, dtype=torch.float32, device=dev)
@@ -740,9 +682,7 @@ class GATLayer(torch.autograd.Function):
             dx = torch.empty(N, K, dtype=torch.float32, device=dev) if need_dx else None
             G = torch.empty(HC, K, dtype=torch.float32, device=dev)
             GV = torch.empty(2, K, dtype=torch.float32, device=dev)
-            nbytes = ctypes.c_size_t(0)
-            _lib.check(lib.ppgat_project_bwd_fused_workspace_bytes(N, ctypes.byref(nbytes)), "project_bwd_fused_ws")
-            ws = torch.empty(max(int(nbytes.value), 1), dtype=torch.uint8, device=dev)
+            ws, nbytes = _lib.workspace(lib.ppgat_project_bwd_fused_workspace_bytes, N, device=dev, floor=1)
             x0, x1, sp = (x, xi, split) if seg else (x, None, N)
             if seg and split == 0:  # no user rows: every row from the item segment
                 x0, x1, sp = xi, None, N
@@ -756,13 +696,13 @@ class GATLayer(torch.autograd.Function):
                     D.data_ptr(), HC, S.data_ptr(), 2, x0.data_ptr(), K, _lib.ptr(x1), K, sp, N, K, W.data_ptr(), K,
                     a_s.data_ptr(), a_d.data_ptr(), dx.data_ptr(), K, G.data_ptr(), GV.data_ptr(), _lib.ptr(pb),
                     ps_dst.data_ptr(), pm.data_ptr(), pinv_l.data_ptr(), 1.0, p_nstate.data_ptr(), _lib.ptr(p_dbias),
-                    ws.data_ptr(), nbytes.value, _lib.stream_handle(dev)), "project_bwd_fused_producer")
+                    ws.data_ptr(), nbytes, _lib.stream_handle(dev)), "project_bwd_fused_producer")
                 prod.pro_result = (weakref.ref(dx), dx._version, p_nstate, p_dbias)
             else:
                 _lib.check(lib.ppgat_project_bwd_fused(D.data_ptr(), HC, S.data_ptr(), 2, x0.data_ptr(), K,
                                                        _lib.ptr(x1), K, sp, N, K, W.data_ptr(), K, a_s.data_ptr(),
                                                        a_d.data_ptr(), _lib.ptr(dx), K, G.data_ptr(), GV.data_ptr(),
-                                                       ws.data_ptr(), nbytes.value, _lib.stream_handle(dev)),
+                                                       ws.data_ptr(), nbytes, _lib.stream_handle(dev)),
                            "project_bwd_fused")
             dW, datt_src, datt_dst = weight_grads(G, GV, W, a_s, a_d, heads, C)
             dx_u = dx[:split] if (dx is not None and had_items) else dx
@@ -889,9 +829,7 @@ def gemm_tn(A: torch.Tensor, B: torch.Tensor, want_colsum: bool = False, V: Opti
     out = torch.empty(M, K, dtype=torch.float32, device=A.device)
     cs = torch.empty(M, dtype=torch.float32, device=A.device) if want_colsum else None
     vout = torch.empty(max(nv, 1), K, dtype=torch.float32, device=A.device) if nv else None
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(lib.ppgat_gemm_tn_workspace_bytes(N, M, K, nv, ctypes.byref(nbytes)), "gemm_tn_workspace_bytes")
-    ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=A.device)
+    ws, nbytes = _lib.workspace(lib.ppgat_gemm_tn_workspace_bytes, N, M, K, nv, device=A.device)
     lda = A.stride(0) if N > 1 else max(M + (-M) % 4, 4)
     ldb = B.stride(0) if split > 1 else max(K + (-K) % 4, 4)
     ldv = (V.stride(0) if N > 1 else nv) if nv else 0
@@ -899,12 +837,12 @@ def gemm_tn(A: torch.Tensor, B: torch.Tensor, want_colsum: bool = False, V: Opti
         ldb1 = B_items.stride(0) if B_items.size(0) > 1 else max(K + (-K) % 4, 4)
         _lib.check(lib.ppgat_gemm_tn_seg(A.data_ptr(), lda, B.data_ptr(), ldb, B_items.data_ptr(), ldb1, split, N, M,
                                          K, out.data_ptr(), _lib.ptr(cs), _lib.ptr(V) if nv else None, ldv, nv,
-                                         _lib.ptr(vout), ws.data_ptr(), nbytes.value, _lib.stream_handle(A.device)),
+                                         _lib.ptr(vout), ws.data_ptr(), nbytes, _lib.stream_handle(A.device)),
                    "gemm_tn")
     else:
         _lib.check(lib.ppgat_gemm_tn(A.data_ptr(), lda, B.data_ptr(), ldb, N, M, K, out.data_ptr(), _lib.ptr(cs),
                                      _lib.ptr(V) if nv else None, ldv, nv, _lib.ptr(vout), ws.data_ptr(),
-                                     nbytes.value, _lib.stream_handle(A.device)), "gemm_tn")
+                                     nbytes, _lib.stream_handle(A.device)), "gemm_tn")
     return out, cs, vout
 
 
@@ -1141,9 +1079,7 @@ def gemm_tn_big(A: torch.Tensor, B: torch.Tensor, b_bound=None, a_bits=None, wan
     _check_rows("B", B, torch.float32, A.device)
     M, ma = A.shape
     nb = B.size(1)
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(lib.ppgat_gemm_tn_big_workspace_bytes(M, ma, nb, ctypes.byref(nbytes)), "gemm_tn_big_workspace")
-    ws = torch.empty(max(int(nbytes.value), 1), dtype=torch.uint8, device=A.device)
+    ws, nbytes = _lib.workspace(lib.ppgat_gemm_tn_big_workspace_bytes, M, ma, nb, device=A.device, floor=1)
     out = torch.empty(ma, nb, dtype=torch.float32, device=A.device)
     lda, ldb, st = A.stride(0) if M > 1 else ma, B.stride(0) if M > 1 else nb, _lib.stream_handle(A.device)
     if want_colsum:
@@ -1157,7 +1093,7 @@ def gemm_tn_big(A: torch.Tensor, B: torch.Tensor, b_bound=None, a_bits=None, wan
         cs = torch.empty(ma, dtype=torch.float32, device=A.device)
         _lib.check(lib.ppgat_gemm_tn_big_colsum(A.data_ptr(), lda, B.data_ptr(), ldb, M, ma, nb, _lib.ptr(a_bits),
                                                 _lib.ptr(bits), int(period), float(scale), out.data_ptr(),
-                                                cs.data_ptr(), ws.data_ptr(), nbytes.value, st), "gemm_tn_big_colsum")
+                                                cs.data_ptr(), ws.data_ptr(), nbytes, st), "gemm_tn_big_colsum")
         return out, cs
     if a_bits is not None:
         _require(a_bits.dtype == torch.int32 and a_bits.numel() == ma and a_bits.device == A.device,
@@ -1165,7 +1101,7 @@ def gemm_tn_big(A: torch.Tensor, B: torch.Tensor, b_bound=None, a_bits=None, wan
         bits, period, scale = b_bound if b_bound is not None else (None, 1, 1.0)
         _lib.check(lib.ppgat_gemm_tn_big_bounds(A.data_ptr(), lda, B.data_ptr(), ldb, M, ma, nb, a_bits.data_ptr(),
                                                 _lib.ptr(bits), int(period), float(scale), out.data_ptr(),
-                                                ws.data_ptr(), nbytes.value, st), "gemm_tn_big_bounds")
+                                                ws.data_ptr(), nbytes, st), "gemm_tn_big_bounds")
         return out
     if b_bound is not None:
         bits, period, scale = b_bound
@@ -1173,10 +1109,10 @@ def gemm_tn_big(A: torch.Tensor, B: torch.Tensor, b_bound=None, a_bits=None, wan
                  "gemm_tn_big: b_bound bits must be int32 [period] on A's device")
         _lib.check(lib.ppgat_gemm_tn_big_bounded(A.data_ptr(), lda, B.data_ptr(), ldb, M, ma, nb, bits.data_ptr(),
                                                  int(period), float(scale), out.data_ptr(), ws.data_ptr(),
-                                                 nbytes.value, st), "gemm_tn_big_bounded")
+                                                 nbytes, st), "gemm_tn_big_bounded")
         return out
     _lib.check(lib.ppgat_gemm_tn_big(A.data_ptr(), lda, B.data_ptr(), ldb, M, ma, nb, out.data_ptr(), ws.data_ptr(),
-                                     nbytes.value, st), "gemm_tn_big")
+                                     nbytes, st), "gemm_tn_big")
     return out
 
 
@@ -1191,12 +1127,10 @@ def colsum(Y: torch.Tensor) -> torch.Tensor:
         return torch.cat([colsum(Y[:, s:s + 128]) for s in range(0, c, 128)])
     if c not in (128, 256):
         return Y.sum(0)
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(lib.ppgat_colsum_workspace_bytes(n, c, ctypes.byref(nbytes)), "colsum_workspace")
-    ws = torch.empty(max(int(nbytes.value), 1), dtype=torch.uint8, device=Y.device)
+    ws, nbytes = _lib.workspace(lib.ppgat_colsum_workspace_bytes, n, c, device=Y.device, floor=1)
     out = torch.empty(c, dtype=torch.float32, device=Y.device)
     _lib.check(lib.ppgat_colsum(Y.data_ptr(), Y.stride(0) if n > 1 else c, n, c, out.data_ptr(), ws.data_ptr(),
-                                nbytes.value, _lib.stream_handle(Y.device)), "colsum")
+                                nbytes, _lib.stream_handle(Y.device)), "colsum")
     return out
 
 
@@ -1235,42 +1169,6 @@ def xgat_supported(in_channels: int, heads: int, channels: int) -> bool:
     return bool(_lib.load().ppgat_xgat_supported(int(in_channels), int(heads), int(channels)))
 
 
-def _xgat_edges_bwd(lib, sched: Schedule, v: "XViews", base_row: int, x, s_src, nstate, gt, A, S, dz, dx, H, K,
-                    slope, p, seed, seed_buf, st):
-    """ppgat_xgat_bwd_edges over one source schedule whose rows start at base_row."""
-    dev = x.device
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(lib.ppgat_xgat_bwd_workspace_bytes(sched.n_hub_items, K, ctypes.byref(nbytes)), "xgat_ws")
-    ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev)
-    cs = sched.cstruct()
-    E = v.n_edges
-    _lib.check(lib.ppgat_xgat_bwd_edges(ctypes.byref(cs), _lib.ptr(v.row) if E else None,
-                                        _lib.ptr(v.csc_eid) if E else None, _lib.ptr(v.dz_slot) if E else None, E, K, H,
-                                        x.data_ptr() + 4 * base_row * K, K, s_src.data_ptr() + 4 * base_row * H,
-                                        nstate.data_ptr(), gt.data_ptr(), A.data_ptr(), float(slope), float(p),
-                                        int(seed) & (2**64 - 1), _lib.ptr(seed_buf), dx.data_ptr() + 4 * base_row * K,
-                                        K, S.data_ptr() + 4 * base_row * 2 * H, 2 * H, dz.data_ptr(), ws.data_ptr(),
-                                        nbytes.value, st), "xgat_bwd_edges")
-
-
-def _xgat_edges_bwd_g(lib, sched: Schedule, v: "XViews", base_row: int, hs, s_src, nstate, g, acc, S, dz, H, C,
-                      slope, p, seed, seed_buf, st):
-    """ppgat_xgat_bwd_edges_g over one source schedule whose rows start at base_row."""
-    dev = hs.device
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(lib.ppgat_xgat_bwd_g_workspace_bytes(sched.n_hub_items, C, H, ctypes.byref(nbytes)), "xgat_g_ws")
-    ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev)
-    cs = sched.cstruct()
-    E = v.n_edges
-    _lib.check(lib.ppgat_xgat_bwd_edges_g(ctypes.byref(cs), _lib.ptr(v.row) if E else None,
-                                          _lib.ptr(v.csc_eid) if E else None, _lib.ptr(v.dz_slot) if E else None, E, C,
-                                          H, hs.data_ptr() + 4 * base_row * H * C, s_src.data_ptr() + 4 * base_row * H,
-                                          nstate.data_ptr(), g.data_ptr(), C, float(slope), float(p),
-                                          int(seed) & (2**64 - 1), _lib.ptr(seed_buf),
-                                          acc.data_ptr() + 4 * base_row * H * C, S.data_ptr() + 4 * base_row * 2 * H,
-                                          2 * H, dz.data_ptr(), ws.data_ptr(), nbytes.value, st), "xgat_bwd_edges_g")
-
-
 @dataclass
 class XPhase:
     """One step of a phased aggregate-then-transform forward (dist._HaloLayerX): the destination
@@ -1288,28 +1186,19 @@ class XPhase:
 
 def xgat_att_proj(weight, att_src, att_dst, heads: int, C: int) -> torch.Tensor:
     """A [2, H, K]: A_v[h] = W_h^T att_v[h] (ppgat_xgat_weights) -- the node scores are x . A."""
-    lib = _lib.load()
     W = weight.detach().contiguous()
-    K = W.size(1)
     a_s = att_src.detach().reshape(heads, C).contiguous()
     a_d = att_dst.detach().reshape(heads, C).contiguous()
-    A = torch.empty(2, heads, K, dtype=torch.float32, device=W.device)
-    _lib.check(lib.ppgat_xgat_weights(W.data_ptr(), a_s.data_ptr(), a_d.data_ptr(), heads, C, K, A.data_ptr(), None,
-                                      None, _lib.stream_handle(W.device)), "xgat_weights")
+    A = torch.empty(2, heads, W.size(1), dtype=torch.float32, device=W.device)
+    _launch.xgat_weights(W, a_s, a_d, heads, C, A=A)
     return A
 
 
 def xgat_scores_rows(x_rows, A, s_src, s_dst=None):
     """s_src (and, given, s_dst) [n, H] of the rows x_rows [n, K] (row stride x_rows.stride(0))
     under A [2, H, K] (ppgat_xgat_scores; per row the same arithmetic whatever the launch)."""
-    lib = _lib.load()
-    n, K = x_rows.shape
-    H = A.size(1)
-    if n:
-        _lib.check(lib.ppgat_xgat_scores(x_rows.data_ptr(), x_rows.stride(0), n, n if s_dst is not None else 0, K, H,
-                                         A.data_ptr(), s_src.data_ptr(),
-                                         s_dst.data_ptr() if s_dst is not None else None,
-                                         _lib.stream_handle(x_rows.device)), "xgat_scores")
+    if x_rows.size(0):
+        _launch.xgat_scores(x_rows, 0, x_rows.size(0), A, s_src, s_dst)
 
 
 def xgat_forward(x, weight, att_src, att_dst, bias, v: "XViews", heads: int, C: int, slope: float, p: float,
@@ -1326,7 +1215,6 @@ def xgat_forward(x, weight, att_src, att_dst, bias, v: "XViews", heads: int, C: 
     (the halo partition: the owners computed them with the rows and sent them along, ready by
     each phase's ``before``) -- no score pass here.  ``keep_agg``: keep the aggregates for the
     backward (None: _xgat_keep_agg decides; the halo partition's backward needs them)."""
-    lib = _lib.load()
     x = x.contiguous()
     dev = x.device
     K = x.size(1)
@@ -1336,11 +1224,9 @@ def xgat_forward(x, weight, att_src, att_dst, bias, v: "XViews", heads: int, C: 
     a_s = att_src.detach().reshape(H, C).contiguous()
     a_d = att_dst.detach().reshape(H, C).contiguous()
     b = bias.detach().contiguous() if bias is not None else None
-    st = _lib.stream_handle(dev)
     A = torch.empty(2, H, K, dtype=torch.float32, device=dev)
     Wt = torch.empty(H * K, C, dtype=torch.float32, device=dev)
-    _lib.check(lib.ppgat_xgat_weights(W.data_ptr(), a_s.data_ptr(), a_d.data_ptr(), H, C, K, A.data_ptr(),
-                                      Wt.data_ptr(), None, st), "xgat_weights")
+    _launch.xgat_weights(W, a_s, a_d, H, C, A=A, Wt=Wt)
     if phases is None:
         phases = [XPhase(0, v.n_dst, v.fwd_sched, ((v.n_dst, v.n_src),) if v.n_src > v.n_dst else ())]
     if scores is not None:
@@ -1351,8 +1237,7 @@ def xgat_forward(x, weight, att_src, att_dst, bias, v: "XViews", heads: int, C: 
         s_src = torch.empty(v.n_src, H, dtype=torch.float32, device=dev)
         s_dst = torch.empty(max(v.n_dst, 1), H, dtype=torch.float32, device=dev)
         # the destination rows' scores (s_src and s_dst), then each phase's other sources
-        _lib.check(lib.ppgat_xgat_scores(x.data_ptr(), K, v.n_dst, v.n_dst, K, H, A.data_ptr(), s_src.data_ptr(),
-                                         s_dst.data_ptr(), st), "xgat_scores")
+        _launch.xgat_scores(x, 0, v.n_dst, A, s_src, s_dst)
     agg = torch.empty(v.n_dst, H, K, dtype=torch.float32, device=dev)
     m = torch.empty(v.n_dst, H, dtype=torch.float32, device=dev)
     inv_l = torch.empty(v.n_dst, H, dtype=torch.float32, device=dev)
@@ -1369,20 +1254,10 @@ def xgat_forward(x, weight, att_src, att_dst, bias, v: "XViews", heads: int, C: 
             ph.before()
         for r0, r1 in (ph.src_ranges if scores is None else ()):
             if r1 > r0:
-                _lib.check(lib.ppgat_xgat_scores(x.data_ptr() + 4 * r0 * K, K, r1 - r0, 0, K, H, A.data_ptr(),
-                                                 s_src.data_ptr() + 4 * r0 * H, None, st), "xgat_scores")
+                _launch.xgat_scores(x, r0, r1 - r0, A, s_src)
         nd = ph.d1 - ph.d0
-        nbytes = ctypes.c_size_t(0)
-        _lib.check(lib.ppgat_xgat_fwd_workspace_bytes(ph.sched.n_hub_items, H, K, ctypes.byref(nbytes)), "xgat_ws")
-        ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev)
-        cs = ph.sched.cstruct()
-        _lib.check(lib.ppgat_xgat_fwd_colmax(ctypes.byref(cs), _lib.ptr(v.col) if E else None,
-                                             _lib.ptr(v.csr_eid) if E else None, nd, E, K, H, x.data_ptr(), K,
-                                             s_src.data_ptr(), s_dst.data_ptr() + 4 * ph.d0 * H, float(slope),
-                                             float(p), int(seed) & (2**64 - 1), _lib.ptr(seed_buf),
-                                             agg.data_ptr() + 4 * ph.d0 * H * K, m.data_ptr() + 4 * ph.d0 * H,
-                                             inv_l.data_ptr() + 4 * ph.d0 * H, xbits.data_ptr(), ws.data_ptr(),
-                                             nbytes.value, st), "xgat_fwd_colmax")
+        _launch.xgat_fwd_colmax(ph.sched, v, ph.d0, nd, x, s_src, s_dst, slope, p, seed, seed_buf, agg, m, inv_l,
+                                xbits)
         if nd > 0:
             gemm_nn(agg[ph.d0:ph.d1].view(nd, H * K), Wt, 0, C, alpha=1.0 / H, bias=b, out=out[ph.d0:ph.d1])
         if ph.after is not None:
@@ -1422,12 +1297,10 @@ def xgat_backward(saved: dict, g: torch.Tensor, want_bias_grad: bool, halo_hook=
     and halo sources (XViews.bwd_sched_own / bwd_sched_halo), the halo rows' input gradients
     are finished first and handed to halo_hook(dx_halo) -- which starts returning them to
     their owners -- before the own rows' edge pass and the weight-gradient GEMMs run."""
-    lib = _lib.load()
     x, W, a_s, a_d, A = saved["x"], saved["W"], saved["a_s"], saved["a_d"], saved["A"]
     s_src, s_dst, agg, m, inv_l, v = saved["s_src"], saved["s_dst"], saved["agg"], saved["m"], saved["inv_l"], saved["v"]
     H, C, K, slope, p, seed, has_bias = saved["meta"]
     dev = x.device
-    st = _lib.stream_handle(dev)
     g = g.contiguous()
     E = v.n_edges
     S = torch.zeros(v.n_src, 2 * H, dtype=torch.float32, device=dev)
@@ -1435,13 +1308,11 @@ def xgat_backward(saved: dict, g: torch.Tensor, want_bias_grad: bool, halo_hook=
     nstate = torch.empty(max(v.n_dst, 1), H, 4, dtype=torch.float32, device=dev)
     mode = _xgat_gather_mode(C, H, v.n_src, v.n_dst, E, K)
     if mode == "gd":
-        return _xgat_backward_deferred_d(lib, saved, g, S, dz, nstate, want_bias_grad, halo_hook, st)
+        return _xgat_backward_deferred_d(saved, g, S, dz, nstate, want_bias_grad, halo_hook)
     Wg = torch.empty(C, H * K, dtype=torch.float32, device=dev)
-    _lib.check(lib.ppgat_xgat_weights(W.data_ptr(), None, None, H, C, K, None, None, Wg.data_ptr(), st),
-               "xgat_weights")
+    _launch.xgat_weights(W, None, None, H, C, Wg=Wg)
     gt = gemm_nn(g, Wg, 0, H * K)
-    _lib.check(lib.ppgat_xgat_bwd_prologue(gt.data_ptr(), agg.data_ptr(), s_dst.data_ptr(), m.data_ptr(),
-                                           inv_l.data_ptr(), v.n_dst, K, H, nstate.data_ptr(), st), "xgat_bwd_prologue")
+    _launch.xgat_bwd_prologue(gt, agg, s_dst, m, inv_l, v.n_dst, K, H, nstate)
     if mode == "g":
         # gather g_i per edge (C floats) instead of gt_i (H * C_in): hs = x W^T / H per source,
         # the per-head message gradient acc [n_src, H * C], then dx = acc W / H + S A_att with the
@@ -1450,40 +1321,39 @@ def xgat_backward(saved: dict, g: torch.Tensor, want_bias_grad: bool, halo_hook=
         acc = torch.empty(v.n_src, H * C, dtype=torch.float32, device=dev)
         dx = torch.empty(v.n_src, K, dtype=torch.float32, device=dev)
         A2 = A.view(2 * H, K)
-        gargs = (hs, s_src, nstate, g, acc, S, dz, H, C, slope, p, seed, saved["seed_buf"], st)
+        gargs = (hs, s_src, nstate, g, acc, S, dz, H, C, slope, p, seed, saved["seed_buf"])
         n0 = v.n_dst
         if halo_hook is not None and v.bwd_sched_halo is not None:
             # the halo sources first: their rows of dx (no destination terms) go back to their
             # owners while the own sources' edge pass runs
-            _xgat_edges_bwd_g(lib, v.bwd_sched_halo, v, n0, *gargs)
+            _launch.xgat_bwd_edges_g(v.bwd_sched_halo, v, n0, *gargs)
             if v.n_src > n0:
                 gemm_nn(acc[n0:], W, 0, K, alpha=1.0 / H, out=dx[n0:], rank=(S[n0:, :H], A2[:H]))
             halo_hook(dx[n0:])
-            _xgat_edges_bwd_g(lib, v.bwd_sched_own, v, 0, *gargs)
-            _xgat_dst_sum(lib, v, dz, S, H, E, st)
+            _launch.xgat_bwd_edges_g(v.bwd_sched_own, v, 0, *gargs)
+            _xgat_dst_sum(v, dz, S[:, H:], H)
             gemm_nn(acc[:n0], W, 0, K, alpha=1.0 / H, out=dx[:n0], rank=(S[:n0], A2))
         else:
-            _xgat_edges_bwd_g(lib, v.bwd_sched, v, 0, *gargs)
-            _xgat_dst_sum(lib, v, dz, S, H, E, st)
+            _launch.xgat_bwd_edges_g(v.bwd_sched, v, 0, *gargs)
+            _xgat_dst_sum(v, dz, S[:, H:], H)
             gemm_nn(acc, W, 0, K, alpha=1.0 / H, out=dx, rank=(S, A2))  # + sum_h ds_src^h A_src^h + ds_dst^h A_dst^h
             if halo_hook is not None:
                 halo_hook(dx[n0:])
         del hs, acc
-        return _xgat_weight_grads(lib, saved, g, S, dx, want_bias_grad, st)
+        return _xgat_weight_grads(None, saved, g, S, dx, want_bias_grad, None)
     dx = torch.empty(v.n_src, K, dtype=torch.float32, device=dev)
-    args = (x, s_src, nstate, gt, A, S, dz, dx, H, K, slope, p, seed, saved["seed_buf"], st)
+    args = (x, s_src, nstate, gt, A, S, dz, dx, H, slope, p, seed, saved["seed_buf"])
     if halo_hook is not None and v.bwd_sched_halo is not None:
-        _xgat_edges_bwd(lib, v.bwd_sched_halo, v, v.n_dst, *args)
+        _launch.xgat_bwd_edges(v.bwd_sched_halo, v, v.n_dst, *args)
         halo_hook(dx[v.n_dst:])
-        _xgat_edges_bwd(lib, v.bwd_sched_own, v, 0, *args)
+        _launch.xgat_bwd_edges(v.bwd_sched_own, v, 0, *args)
     else:
-        _xgat_edges_bwd(lib, v.bwd_sched, v, 0, *args)
+        _launch.xgat_bwd_edges(v.bwd_sched, v, 0, *args)
         if halo_hook is not None:
             halo_hook(dx[v.n_dst:])
-    _xgat_dst_sum(lib, v, dz, S, H, E, st)
-    _lib.check(lib.ppgat_xgat_bwd_epilogue(S.data_ptr(), 2 * H, A.data_ptr(), v.n_dst, K, H, dx.data_ptr(), K, st),
-               "xgat_bwd_epilogue")
-    return _xgat_weight_grads(lib, saved, g, S, dx, want_bias_grad, st)
+    _xgat_dst_sum(v, dz, S[:, H:], H)
+    _launch.xgat_bwd_epilogue(S, A, v.n_dst, H, dx)
+    return _xgat_weight_grads(None, saved, g, S, dx, want_bias_grad, None)
 
 
 def _xgat_bytes(mode: str, n_src: int, n_dst: int, n_edges: int, C: int, H: int, K: int) -> float:
@@ -1516,7 +1386,7 @@ def _xgat_gather_mode(C: int, H: int, n_src: Optional[int] = None, n_dst: Option
     return "gd"
 
 
-def _xgat_backward_deferred_d(lib, saved: dict, g, S, dz, nstate, want_bias_grad: bool, halo_hook, st):
+def _xgat_backward_deferred_d(saved: dict, g, S, dz, nstate, want_bias_grad: bool, halo_hook):
     """The default multi-head backward: D^h_i = sum_j beta dalpha from the edge
     pass itself instead of gt^h_i . agg^h_i, so neither gt = g W_grad nor its prologue runs."""
     x, W, A = saved["x"], saved["W"], saved["A"]
@@ -1526,8 +1396,7 @@ def _xgat_backward_deferred_d(lib, saved: dict, g, S, dz, nstate, want_bias_grad
     E = v.n_edges
     n0 = v.n_dst
     seed_buf = saved["seed_buf"]
-    _lib.check(lib.ppgat_xgat_nstate(s_dst.data_ptr(), m.data_ptr(), inv_l.data_ptr(), None, n0, H,
-                                     nstate.data_ptr(), st), "xgat_nstate")
+    _launch.xgat_nstate(s_dst, m, inv_l, None, n0, H, nstate)
     hs = gemm_nn(x, W, 1, H * C, alpha=1.0 / H)
     acc = torch.empty(v.n_src, H * C, dtype=torch.float32, device=dev)
     pdal = torch.empty(max(E, 1) * H, dtype=torch.float32, device=dev)
@@ -1535,83 +1404,47 @@ def _xgat_backward_deferred_d(lib, saved: dict, g, S, dz, nstate, want_bias_grad
     split = halo_hook is not None and v.bwd_sched_halo is not None
     scheds = [(v.bwd_sched_halo, n0), (v.bwd_sched_own, 0)] if split else [(v.bwd_sched, 0)]
     for sched, base in scheds:  # dalpha (into dz) and beta dalpha per edge, acc per source
-        nbytes = ctypes.c_size_t(0)
-        _lib.check(lib.ppgat_xgat_bwd_g_workspace_bytes(sched.n_hub_items, C, H, ctypes.byref(nbytes)), "xgat_g_ws")
-        ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev)
-        cs = sched.cstruct()
-        _lib.check(lib.ppgat_xgat_bwd_edges_gd_colmax(ctypes.byref(cs), _lib.ptr(v.row) if E else None,
-                                                      _lib.ptr(v.csc_eid) if E else None,
-                                                      _lib.ptr(v.dz_slot) if E else None, E, C, H,
-                                                      hs.data_ptr() + 4 * base * H * C, s_src.data_ptr() + 4 * base * H,
-                                                      nstate.data_ptr(), g.data_ptr(), C, float(slope), float(p),
-                                                      int(seed) & (2**64 - 1), _lib.ptr(seed_buf),
-                                                      acc.data_ptr() + 4 * base * H * C, dz.data_ptr(),
-                                                      pdal.data_ptr(), gbits.data_ptr(), ws.data_ptr(), nbytes.value,
-                                                      st), "xgat_bwd_edges_gd_colmax")
+        _launch.xgat_bwd_edges_gd_colmax(sched, v, base, hs, s_src, nstate, g, acc, dz, pdal, gbits, H, C, slope, p,
+                                         seed, seed_buf)
     del hs
     D = torch.empty(max(n0, 1), H, dtype=torch.float32, device=dev)
-    _xgat_dst_sum(lib, v, pdal, D, H, E, st, col0=0, ld=H)  # D_i = sum_j beta dalpha
+    _xgat_dst_sum(v, pdal, D, H)  # D_i = sum_j beta dalpha
     del pdal
-    _lib.check(lib.ppgat_xgat_nstate(s_dst.data_ptr(), m.data_ptr(), inv_l.data_ptr(), D.data_ptr(), n0, H,
-                                     nstate.data_ptr(), st), "xgat_nstate")
-
-    def dz_pass(sched, base):  # dz in place over dalpha, ds_src into S[:, :H]
-        nbytes = ctypes.c_size_t(0)
-        _lib.check(lib.ppgat_xgat_bwd_dz_workspace_bytes(sched.n_hub_items, H, ctypes.byref(nbytes)), "xgat_dz_ws")
-        ws = torch.empty(max(int(nbytes.value), 4), dtype=torch.uint8, device=dev)
-        cs = sched.cstruct()
-        _lib.check(lib.ppgat_xgat_bwd_dz(ctypes.byref(cs), _lib.ptr(v.row) if E else None,
-                                         _lib.ptr(v.csc_eid) if E else None, _lib.ptr(v.dz_slot) if E else None, E, H,
-                                         s_src.data_ptr() + 4 * base * H, nstate.data_ptr(), float(slope), float(p),
-                                         int(seed) & (2**64 - 1), _lib.ptr(seed_buf), dz.data_ptr(),
-                                         S.data_ptr() + 4 * base * 2 * H, 2 * H, ws.data_ptr(), nbytes.value, st),
-                   "xgat_bwd_dz")
-
+    _launch.xgat_nstate(s_dst, m, inv_l, D, n0, H, nstate)
+    dza = (s_src, nstate, dz, S, H, slope, p, seed, seed_buf)  # the dz pass: dz in place over dalpha, ds_src into S
     dx = torch.empty(v.n_src, K, dtype=torch.float32, device=dev)
     A2 = A.view(2 * H, K)
     if split:
         # the halo sources first: their rows of dx (no destination terms) go back to their owners
         # while the own sources' dz pass, the destination sums and the GEMMs run
-        dz_pass(v.bwd_sched_halo, n0)
+        _launch.xgat_bwd_dz(v.bwd_sched_halo, v, n0, *dza)
         if v.n_src > n0:
             gemm_nn(acc[n0:], W, 0, K, alpha=1.0 / H, out=dx[n0:], rank=(S[n0:, :H], A2[:H]))
         halo_hook(dx[n0:])
-        dz_pass(v.bwd_sched_own, 0)
-        _xgat_dst_sum(lib, v, dz, S, H, E, st)
+        _launch.xgat_bwd_dz(v.bwd_sched_own, v, 0, *dza)
+        _xgat_dst_sum(v, dz, S[:, H:], H)
         gemm_nn(acc[:n0], W, 0, K, alpha=1.0 / H, out=dx[:n0], rank=(S[:n0], A2))
     else:
-        dz_pass(v.bwd_sched, 0)
-        _xgat_dst_sum(lib, v, dz, S, H, E, st)
+        _launch.xgat_bwd_dz(v.bwd_sched, v, 0, *dza)
+        _xgat_dst_sum(v, dz, S[:, H:], H)
         gemm_nn(acc, W, 0, K, alpha=1.0 / H, out=dx, rank=(S, A2))
         if halo_hook is not None:
             halo_hook(dx[n0:])
     if saved["agg"] is not None:
         del acc
-        return _xgat_weight_grads(lib, saved, g, S, dx, want_bias_grad, st, gbits=gbits)
-    return _xgat_weight_grads(lib, saved, g, S, dx, want_bias_grad, st, acc=acc)
+        return _xgat_weight_grads(None, saved, g, S, dx, want_bias_grad, None, gbits=gbits)
+    return _xgat_weight_grads(None, saved, g, S, dx, want_bias_grad, None, acc=acc)
 
 
-def _xgat_dst_sum(lib, v: "XViews", dz, S, H: int, E: int, st, col0: Optional[int] = None, ld: Optional[int] = None):
-    """Per-destination sums of dz (per edge and head) into S[:, col0:col0 + H] with row stride
-    ld (default: ds_dst into S[:, H:2H], ld 2H), fixed order."""
-    dev = dz.device
-    col0 = H if col0 is None else col0
-    ld = 2 * H if ld is None else ld
-    fs = v.fwd_sched.cstruct()
-    if E > 6 * max(v.n_dst, 1):
-        # a thread per short destination (k_dst_sum_vh_short) pays off on the halo tables' rows of
-        # ~2 edges (4 x 1.48 -> 4 x 0.71 ms per step at the world-8 probe); at the share's ~13 it
-        # measured slower than 16 lanes per item (0.70 vs 0.54 ms per call, profiles/r06/
-        # x13_cfg5_kernel_stats.csv against r05/w43): all items on the 16-lane kernel (same bits)
-        fs.n_long_items = -1
-    dws = torch.empty(max(v.fwd_sched.n_hub_items * H, 1), dtype=torch.float32, device=dev)
-    if v.dz_slot is None:
-        _lib.check(lib.ppgat_bwd_dst_sum_csc(ctypes.byref(fs), v.n_dst, E, H, dz.data_ptr(),
-                                             _lib.ptr(v.csr2csc) if E else None, S.data_ptr() + 4 * col0, ld,
-                                             dws.data_ptr(), dws.numel() * 4, st), "bwd_dst_sum_csc")
-    else:
-        _lib.check(lib.ppgat_bwd_dst_sum(ctypes.byref(fs), v.n_dst, H, dz.data_ptr(), S.data_ptr() + 4 * col0, ld,
-                                         dws.data_ptr(), dws.numel() * 4, st), "bwd_dst_sum")
+def _xgat_dst_sum(v: "XViews", dz, out, H: int):
+    """Per-destination sums of dz (per edge and head) into ``out`` [n_dst, H], fixed order: ds_dst
+    into the column view S[:, H:], or a table of its own."""
+    # a thread per short destination (k_dst_sum_vh_short) pays off on the halo tables' rows of
+    # ~2 edges (4 x 1.48 -> 4 x 0.71 ms per step at the world-8 probe); at the share's ~13 it
+    # measured slower than 16 lanes per item (0.70 vs 0.54 ms per call, profiles/r06/
+    # x13_cfg5_kernel_stats.csv against r05/w43): all items on the 16-lane kernel (same bits)
+    _launch.bwd_dst_sum(v.fwd_sched, v.n_dst, v.n_edges, H, dz, v.csr2csc, out, csc=v.dz_slot is None,
+                        all_long=v.n_edges > 6 * max(v.n_dst, 1))
 
 
 def _xgat_weight_grads(lib, saved: dict, g, S, dx, want_bias_grad: bool, st, x_rows=None, xbits=None, acc=None,
@@ -1620,7 +1453,9 @@ def _xgat_weight_grads(lib, saved: dict, g, S, dx, want_bias_grad: bool, st, x_r
     default all of the layer's source rows; ``xbits``: a column bound of the source rows of x,
     colmax_abs bits -- default the forward's, gathered by its edge pass; ``gbits``: a column bound
     of |g| over the destinations with an in-edge, from the backward's edge pass).  Without a
-    saved agg (_xgat_keep_agg): G from ``acc`` [n_src, H * C] as (acc^T x) permuted."""
+    saved agg (_xgat_keep_agg): G from ``acc`` [n_src, H * C] as (acc^T x) permuted.
+    ``lib`` and ``st`` are not used (the launches find the library and the stream themselves);
+    they keep their places for the tools and tests that wrap this function by position."""
     x, W, a_s, a_d, agg, v = saved["x"], saved["W"], saved["a_s"], saved["a_d"], saved["agg"], saved["v"]
     H, C, K, slope, p, seed, has_bias = saved["meta"]
     dev = x.device
@@ -1632,7 +1467,7 @@ def _xgat_weight_grads(lib, saved: dict, g, S, dx, want_bias_grad: bool, st, x_r
         Gp = gemm_tn_big(acc, x, b_bound=(colmax_abs(x), K, 1.0))
         G = Gp.view(H, C, K).permute(1, 0, 2).reshape(C, H * K).contiguous()
         del Gp
-        return (dx,) + _xgat_weight_grads_from_G(lib, saved, G, GV, g, want_bias_grad, st)
+        return (dx,) + _xgat_weight_grads_from_G(saved, G, GV, g, want_bias_grad)
     # |agg^h_i[k]| = |sum_j beta_ij x_j[k]| <= max_j |x_j[k]| / (1 - p) over i's sources j (the
     # attention weights sum to 1, the kept ones scaled by 1 / (1 - p)): a column bound of agg from
     # the column maxima of the SOURCE rows of x (1 KB per row; a row with no out-edge -- however
@@ -1647,20 +1482,18 @@ def _xgat_weight_grads(lib, saved: dict, g, S, dx, want_bias_grad: bool, st, x_r
         G, gsum = gemm_tn_big(g, agg.view(v.n_dst, H * K), b_bound=xbound, a_bits=gbits, want_colsum=True)
     else:
         G, gsum = gemm_tn_big(g, agg.view(v.n_dst, H * K), b_bound=xbound, a_bits=gbits), None
-    dW, datt_src, datt_dst, dbias = _xgat_weight_grads_from_G(lib, saved, G, GV, g, want_bias_grad, st, gsum)
+    dW, datt_src, datt_dst, dbias = _xgat_weight_grads_from_G(saved, G, GV, g, want_bias_grad, gsum)
     return dx, dW, datt_src, datt_dst, dbias
 
 
-def _xgat_weight_grads_from_G(lib, saved: dict, G, GV, g, want_bias_grad: bool, st, gsum=None):
+def _xgat_weight_grads_from_G(saved: dict, G, GV, g, want_bias_grad: bool, gsum=None):
     W, a_s, a_d = saved["W"], saved["a_s"], saved["a_d"]
     H, C, K, slope, p, seed, has_bias = saved["meta"]
     dev = W.device
     dW = torch.empty_like(W)
     datt_src = torch.empty(H, C, dtype=torch.float32, device=dev)
     datt_dst = torch.empty(H, C, dtype=torch.float32, device=dev)
-    _lib.check(lib.ppgat_xgat_weight_grads(G.data_ptr(), GV.data_ptr(), W.data_ptr(), a_s.data_ptr(), a_d.data_ptr(),
-                                           H, C, K, dW.data_ptr(), datt_src.data_ptr(), datt_dst.data_ptr(), st),
-               "xgat_weight_grads")
+    _launch.xgat_weight_grads(G, GV, W, a_s, a_d, H, C, dW, datt_src, datt_dst)
     dbias = (gsum if gsum is not None else colsum(g)) if (has_bias and want_bias_grad) else None
     return dW, datt_src, datt_dst, dbias
 
@@ -1755,10 +1588,7 @@ class BprPrepared:
             _check_dev("row_map", row_map, torch.int32, dev)
         self.row_map = row_map
         self.meta = (int(n_rows), int(n_users), int(n_items), int(C), self.u.numel())
-        nbytes = ctypes.c_size_t(0)
-        _lib.check(lib.ppgat_bpr_workspace_bytes(int(n_rows), self.u.numel(), int(C), ctypes.byref(nbytes)),
-                   "bpr_workspace_bytes")
-        self.ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev)
+        self.ws, _ = _lib.workspace(lib.ppgat_bpr_workspace_bytes, int(n_rows), self.u.numel(), int(C), device=dev)
         main = torch.cuda.current_stream(dev)
         self.side = _side_stream(dev)
         self.side.wait_stream(main)  # the triples and the workspace come from the current stream
@@ -1813,9 +1643,7 @@ class _BPRLoss(torch.autograd.Function):
             _check_dev("row_map", row_map, torch.int32, Z.device)
         _BadIndex.raise_pending()
         if prep is None:
-            nbytes = ctypes.c_size_t(0)
-            _lib.check(lib.ppgat_bpr_workspace_bytes(n_rows, S, C, ctypes.byref(nbytes)), "bpr_workspace_bytes")
-            ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=Z.device)
+            ws, _ = _lib.workspace(lib.ppgat_bpr_workspace_bytes, n_rows, S, C, device=Z.device)
         loss = torch.empty(1, dtype=torch.float32, device=Z.device)
         coef = torch.empty(max(S, 1), 2, dtype=torch.float32, device=Z.device)
         bad = torch.empty(1, dtype=torch.int32, device=Z.device)
@@ -1915,23 +1743,18 @@ class HipStages:
 
     def gather_rows(self, t, idx):
         """t[idx] (the all_to_all send buffer) through ppgat_rows_gather."""
-        lib = _lib.load()
         _check_dev("rows", t, torch.float32)
         _check_dev("idx", idx, torch.int64, t.device)
         out = torch.empty((idx.numel(),) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
         cols = t[0].numel() if t.size(0) else (out[0].numel() if idx.numel() else 0)
-        _lib.check(lib.ppgat_rows_gather(t.data_ptr(), cols, idx.data_ptr(), idx.numel(), cols, out.data_ptr(), cols,
-                                         _lib.stream_handle(t.device)), "rows_gather")
+        _launch.rows_gather(t, idx, cols, out)
         return out
 
     def return_add(self, dst, ret, ptr, pos):
         """dst[o] += ret[pos[ptr[o]:ptr[o+1]]] in order (ppgat_rows_return_add), in place."""
-        lib = _lib.load()
         _check_dev("dst", dst, torch.float32)
         cols = dst[0].numel() if dst.size(0) else 0
-        _lib.check(lib.ppgat_rows_return_add(dst.data_ptr(), cols, ret.data_ptr() if ret.numel() else None, cols,
-                                             ptr.data_ptr(), pos.data_ptr() if pos.numel() else None, dst.size(0),
-                                             cols, _lib.stream_handle(dst.device)), "rows_return_add")
+        _launch.rows_return_add(dst, ret, ptr, pos, cols)
         return dst
 
     bpr_grad_rows = True  # bpr() takes grad_rows (dist.halo_bpr_loss)
@@ -1943,74 +1766,36 @@ class HipStages:
         return node_scores(h, att_src, att_dst, heads, channels)
 
     def fwd(self, v, h_full, s_src_full, s_dst, bias, heads, channels, mode, slope, p, seed, want_agg, seed_buf=None):
-        lib = _lib.load()
         dev = h_full.device
         _tap_kinks(v.rowptr, v.col, v.csr_eid, s_src_full, s_dst, heads)
         R = v.n_rows
-        out = torch.empty(R, channels, dtype=torch.float32, device=dev)
-        m = torch.empty(R, heads, dtype=torch.float32, device=dev)
-        inv_l = torch.empty(R, heads, dtype=torch.float32, device=dev)
-        agg = torch.empty(R, heads, channels, dtype=torch.float32, device=dev) if want_agg else None
-        nbytes = ctypes.c_size_t(0)
-        _lib.check(lib.ppgat_fwd_workspace_bytes(v.fwd_sched.n_hub_items, heads, channels, ctypes.byref(nbytes)),
-                   "fwd_workspace_bytes")
-        ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev)
-        cs = v.fwd_sched.cstruct()
-        _lib.check(lib.ppgat_fwd(ctypes.byref(cs), _lib.ptr(v.col) if v.n_fwd_edges else None,
-                                 _lib.ptr(v.csr_eid) if v.n_fwd_edges else None, R, v.n_fwd_edges, heads, channels,
-                                 h_full.data_ptr(), s_src_full.data_ptr(), s_dst.data_ptr(), _lib.ptr(bias), mode,
-                                 float(slope), float(p), int(seed) & (2**64 - 1), _lib.ptr(seed_buf), out.data_ptr(),
-                                 m.data_ptr(), inv_l.data_ptr(), _lib.ptr(agg), ws.data_ptr(), nbytes.value,
-                                 _lib.stream_handle(dev)), "gat_fwd")
+        out, m, inv_l, agg = _fwd_outputs(R, heads, channels, want_agg, dev)
+        _launch.fwd(v.fwd_sched, v.col, v.csr_eid, v.n_fwd_edges, 0, R, h_full, s_src_full, s_dst, bias, heads,
+                    channels, mode, slope, p, seed, seed_buf, out, m, inv_l, agg)
         return out, m, inv_l, agg
 
     def bwd_prologue(self, grad_out, out, agg, bias, s_dst, m, inv_l, heads, channels, mode, want_bias_grad):
-        lib = _lib.load()
         dev = grad_out.device
         R = grad_out.size(0)
         nstate = torch.empty(R, heads, 4, dtype=torch.float32, device=dev)
         dbias = torch.empty(channels, dtype=torch.float32, device=dev) if want_bias_grad else None
-        rows = int(lib.ppgat_bwd_partial_rows(R))
-        part = torch.empty(max(rows, 1) * channels, dtype=torch.float32, device=dev) if want_bias_grad else None
-        _lib.check(lib.ppgat_bwd_prologue(grad_out.data_ptr(), out.data_ptr(), _lib.ptr(agg), _lib.ptr(bias),
-                                          s_dst.data_ptr(), m.data_ptr(), inv_l.data_ptr(), R, heads, channels, mode,
-                                          nstate.data_ptr(), _lib.ptr(dbias), _lib.ptr(part),
-                                          _lib.stream_handle(dev)), "bwd_prologue")
+        _launch.bwd_prologue(0, R, grad_out, out, agg, bias, s_dst, m, inv_l, heads, channels, mode, nstate, dbias)
         return nstate, dbias
 
     def bwd_edges(self, v, h, s_src, nstate_full, grad_out_full, dz, heads, channels, mode, slope, p, seed,
                   seed_buf=None):
-        lib = _lib.load()
         dev = h.device
         R = v.n_rows
         grad_h = torch.empty(R, heads * channels, dtype=torch.float32, device=dev)
         ds_src = torch.empty(R, heads, dtype=torch.float32, device=dev)
-        nbytes = ctypes.c_size_t(0)
-        _lib.check(lib.ppgat_fwd_workspace_bytes(v.bwd_sched.n_hub_items, heads, channels, ctypes.byref(nbytes)),
-                   "workspace_bytes")
-        ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev)
-        cs = v.bwd_sched.cstruct()
-        E = v.n_bwd_edges
-        _lib.check(lib.ppgat_bwd_edges(ctypes.byref(cs), _lib.ptr(v.row) if E else None,
-                                       _lib.ptr(v.csc_eid) if E else None, _lib.ptr(v.dz_slot) if E else None, E,
-                                       heads, channels, h.data_ptr(), s_src.data_ptr(), nstate_full.data_ptr(),
-                                       grad_out_full.data_ptr(), mode, float(slope), float(p),
-                                       int(seed) & (2**64 - 1), _lib.ptr(seed_buf), grad_h.data_ptr(),
-                                       heads * channels,
-                                       ds_src.data_ptr(), heads, dz.data_ptr(), ws.data_ptr(), nbytes.value,
-                                       _lib.stream_handle(dev)), "bwd_edges")
+        _launch.bwd_edges(v.bwd_sched, v.row, v.csc_eid, v.dz_slot, v.n_bwd_edges, 0, h, s_src, nstate_full,
+                          grad_out_full, heads, channels, mode, slope, p, seed, seed_buf, grad_h, ds_src, dz)
         return grad_h, ds_src
 
     def bwd_epilogue(self, v, h, att_src, att_dst, ds_src, dz, grad_h, heads, channels):
-        lib = _lib.load()
         dev = h.device
         R = v.n_rows
         datt_src = torch.empty(heads, channels, dtype=torch.float32, device=dev)
         datt_dst = torch.empty(heads, channels, dtype=torch.float32, device=dev)
-        rows = int(lib.ppgat_bwd_partial_rows(R))
-        part = torch.empty(max(rows, 1) * 2 * heads * channels, dtype=torch.float32, device=dev)
-        _lib.check(lib.ppgat_bwd_epilogue(v.rowptr.data_ptr(), R, heads, channels, h.data_ptr(), att_src.data_ptr(),
-                                          att_dst.data_ptr(), ds_src.data_ptr(), dz.data_ptr(), grad_h.data_ptr(),
-                                          datt_src.data_ptr(), datt_dst.data_ptr(), part.data_ptr(),
-                                          _lib.stream_handle(dev)), "bwd_epilogue")
+        _launch.bwd_epilogue(v.rowptr, R, heads, channels, h, att_src, att_dst, ds_src, dz, grad_h, datt_src, datt_dst)
         return datt_src, datt_dst
