@@ -487,6 +487,29 @@ int ppgat_sampled_rank(const float* Z, int64_t n_rows, int64_t n_users, int64_t 
                        int channels, const int64_t* users, const int64_t* cands, int64_t n_eval, int64_t n_cand,
                        int32_t* rank, void* stream);
 
+/* ---- full-catalogue ranking (evaluation) ---------------------------------------------
+ * The full-ranking protocol of the LightGCN literature: the held-out positive against EVERY
+ * item outside the user's train history, not against sampled negatives.  For entry b, with
+ * u = users[b], p = pos[b], X = history(u) + {p} and s(i) = <user_rows[u], item_rows[i]>:
+ *   rank[b] = 1 + #{ i not in X : s(i) > s(p) }      (strict, scripts/train_gat_pyg.py:171)
+ *   ties[b] =     #{ i not in X : s(i) == s(p) }     (nullable; a collapsed model shows here)
+ * Exclusion is by index: the positive's own column is never compared, a history item is dropped
+ * whatever its score, duplicates in a history or a history that holds p change nothing.  Users
+ * may repeat; an empty history is legal.  user_ptr [n_users + 1] / items_sorted: the train
+ * history CSR with each user's items ascending (ppgat_bpr_sampler_prepare's outputs); both NULL
+ * = no history.  Rows: ld_user, ld_item >= channels, 16-byte aligned; the two tables may be
+ * row ranges of one node table.  channels in {32, 64, 128, 256} (ppgat_full_rank_supported).
+ * One fused pass on the matrix cores (bf16 three-term split, fp32 accumulation: fp32 dot-product
+ * accuracy); the score matrix is never written.  Integer adds only: exact and repeatable.
+ * s(p) goes through the same product as every s(i), so equal rows give bitwise equal scores.
+ * The workspace is unused (0 bytes are reported); n_eval == 0 succeeds without a launch. */
+int ppgat_full_rank_supported(int channels);
+int ppgat_full_rank_workspace_bytes(int64_t n_eval, int64_t n_items, int channels, size_t* bytes);
+int ppgat_full_rank(const float* user_rows, int64_t ld_user, int64_t n_users, const float* item_rows, int64_t ld_item,
+                    int64_t n_items, int channels, const int64_t* users, const int64_t* pos, int64_t n_eval,
+                    const int64_t* user_ptr, const int32_t* items_sorted, int32_t* rank, int32_t* ties,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- serving top-K ------------------------------------------------------------------
  * Replaces: RecommenderRuntime.top_k_for_user_items, serving/runtime.py:56-76 (numpy):
  *   user_vec = mean(item_vecs[history]); scores = item_vecs @ user_vec; scores[history] = -1e9;

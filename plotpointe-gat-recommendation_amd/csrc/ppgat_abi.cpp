@@ -962,6 +962,57 @@ int ppgat_sampled_rank(const float* Z, int64_t n_rows, int64_t n_users, int64_t 
   return PPGAT_OK;
 }
 
+int ppgat_full_rank_supported(int channels) { return ppgat::full_rank_channels_ok(channels) ? 1 : 0; }
+
+int ppgat_full_rank_workspace_bytes(int64_t n_eval, int64_t n_items, int channels, size_t* bytes) {
+  if (!bytes || n_eval < 0 || n_items < 1) return fail(PPGAT_ERR_INVALID, "full_rank_workspace_bytes: bad arguments");
+  if (!ppgat::full_rank_channels_ok(channels))
+    return fail(PPGAT_ERR_UNSUPPORTED, "full_rank_workspace_bytes: channels must be 32, 64, 128 or 256");
+  *bytes = 0;  // the counts are added into rank / ties themselves
+  return PPGAT_OK;
+}
+
+int ppgat_full_rank(const float* user_rows, int64_t ld_user, int64_t n_users, const float* item_rows, int64_t ld_item,
+                    int64_t n_items, int channels, const int64_t* users, const int64_t* pos, int64_t n_eval,
+                    const int64_t* user_ptr, const int32_t* items_sorted, int32_t* rank, int32_t* ties,
+                    void* workspace, size_t workspace_bytes, void* stream) {
+  (void)workspace;
+  (void)workspace_bytes;
+  if (!ppgat::full_rank_channels_ok(channels))
+    return fail(PPGAT_ERR_UNSUPPORTED, "full_rank: channels must be 32, 64, 128 or 256");
+  if (n_users < 1 || n_items < 1 || n_eval < 0) return fail(PPGAT_ERR_INVALID, "full_rank: bad sizes");
+  if (n_items >= (int64_t)1 << 31) return fail(PPGAT_ERR_UNSUPPORTED, "full_rank: n_items must be < 2^31 (int32 ranks)");
+  if (ld_user < channels || ld_item < channels || (ld_user & 3) || (ld_item & 3))
+    return fail(PPGAT_ERR_INVALID, "full_rank: ld_user and ld_item must be >= channels and multiples of 4");
+  if (!user_rows || !item_rows || (n_eval > 0 && (!users || !pos || !rank)))
+    return fail(PPGAT_ERR_INVALID, "full_rank: null pointer");
+  if ((reinterpret_cast<uintptr_t>(user_rows) | reinterpret_cast<uintptr_t>(item_rows)) & 15)
+    return fail(PPGAT_ERR_INVALID, "full_rank: rows must be 16-byte aligned");
+  if ((user_ptr == nullptr) != (items_sorted == nullptr))
+    return fail(PPGAT_ERR_INVALID, "full_rank: user_ptr and items_sorted go together (both NULL = no history)");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = debug_range(users, 8, n_eval, 0, n_users, "full_rank: users", st)) return rc;
+  if (int rc = debug_range(pos, 8, n_eval, 0, n_items, "full_rank: pos", st)) return rc;
+#if PPGAT_DEBUG
+  if (user_ptr && n_eval > 0) {  // the CSR's length lives on the device: user_ptr[n_users]
+    int64_t nnz = 0;
+    hipError_t he = hipMemcpyAsync(&nnz, user_ptr + n_users, sizeof(int64_t), hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess) he = hipStreamSynchronize(st);
+    if (he != hipSuccess) return hip_fail(he, "full_rank: user_ptr");
+    if (nnz < 0) return fail(PPGAT_ERR_INVALID, "full_rank: user_ptr ends below 0");
+    if (int rc = debug_range(user_ptr, 8, n_users + 1, 0, nnz + 1, "full_rank: user_ptr", st)) return rc;
+    if (int rc = debug_range(items_sorted, 4, nnz, 0, n_items, "full_rank: items_sorted", st)) return rc;
+  }
+#endif
+  hipError_t e = ppgat::full_rank(user_rows, ld_user, n_users, item_rows, ld_item, n_items, channels, users, pos,
+                                  n_eval, user_ptr, items_sorted, rank, ties, st);
+#if PPGAT_DEBUG
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+#endif
+  if (e != hipSuccess) return hip_fail(e, "full_rank");
+  return PPGAT_OK;
+}
+
 int ppgat_serve_topk_workspace_bytes(int64_t n_items, int channels, int n_users, size_t* bytes) {
   if (!bytes || n_items < 1 || n_users < 0) return fail(PPGAT_ERR_INVALID, "serve_topk_workspace_bytes: bad sizes");
   if (channels != 64 && channels != 128 && channels != 256) return fail(PPGAT_ERR_UNSUPPORTED, "serve_topk: channels");

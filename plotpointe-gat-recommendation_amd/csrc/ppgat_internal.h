@@ -178,6 +178,13 @@ hipError_t sampled_rank(const float* Z, int64_t n_users, int64_t n_items, const 
                         const int64_t* users, const int64_t* cands, int64_t B, int64_t K1, int32_t* rank,
                         hipStream_t st);
 
+// full-catalogue ranking (ppgat_fullrank.hip): rank / ties of pos[b] among every item outside
+// history(users[b]) + {pos[b]}; uptr / hist nullable together; ties nullable
+bool full_rank_channels_ok(int C);
+hipError_t full_rank(const float* U, int64_t ldu, int64_t n_users, const float* I, int64_t ldi, int64_t n_items, int C,
+                     const int64_t* users, const int64_t* pos, int64_t n_eval, const int64_t* uptr,
+                     const int32_t* hist, int32_t* rank, int32_t* ties, hipStream_t st);
+
 // fusion MLP (ppgat_fusion.hip)
 bool fusion_shape_ok(int Dt, int Di, int h1, int d_out);
 size_t fusion_workspace_bytes(int Dt, int Di);

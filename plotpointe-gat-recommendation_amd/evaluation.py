@@ -10,6 +10,10 @@
   device too (``ppgat_eval_sample``: same rule, counter-based stream), so the whole
   evaluation is two kernels and one copy of the ranks; ``fast=True`` draws the same
   distribution with vectorised numpy (different stream).
+* ``eval_full`` / ``full_rank`` -- the full-ranking protocol of the LightGCN literature: the
+  held-out positive against EVERY item outside the user's train history (no sampling, so the
+  metrics are exact and comparable with published ones).  One fused matrix-core pass
+  (``ppgat_full_rank``): the ``[users, items]`` score matrix is never written.
 * ``export_item_embeddings`` -- tools/export_item_embeddings.py:139-145.
 * ``top_k_for_user_items`` / ``top_k_batch`` -- serving/runtime.py:56-76 on the device
   (``ppgat_serve_topk``): user vector = mean of history rows, history masked to -1e9,
@@ -115,6 +119,69 @@ def eval_sampled(model, cfg, item_feats: torch.Tensor, edge_index: torch.Tensor,
     if len(users) == 0:
         return metrics_from_ranks(np.zeros(0, np.int64), Ks)
     ranks = sampled_rank(Z, model.n_users, users, cands)
+    return metrics_from_ranks(ranks, Ks)
+
+
+def full_rank(Z_users: torch.Tensor, Z_items: torch.Tensor, users, pos, sampler=None, return_ties: bool = False):
+    """rank[b] = 1 + #{items i outside history(users[b]) + {pos[b]} : s(i) > s(pos[b])} over the
+    whole catalogue, s(i) = <Z_users[users[b]], Z_items[i]> (strict, as the sampled rule).
+
+    ``Z_users`` [n_users, C] / ``Z_items`` [n_items, C]: fp32 ROCm tensors with dense rows; row or
+    column views of one table are used in place (the leading dimension is ``stride(0)``).
+    ``sampler``: a sampler.BPRSampler over the train lists (its sorted history CSR is the
+    excluded set); None = nothing but the positive is excluded.  ``return_ties`` adds the count
+    of non-excluded items whose score EQUALS the positive's (a collapsed model shows there: the
+    strict rule ranks every user first when all scores are equal)."""
+    lib = _lib.load()
+    for t in (Z_users, Z_items):
+        if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2:
+            raise RuntimeError("full_rank: 2-D fp32 ROCm tensors required (no CPU path)")
+    if Z_users.size(1) != Z_items.size(1) or Z_users.device != Z_items.device:
+        raise ValueError("full_rank: Z_users and Z_items differ in width or device")
+    dev = Z_users.device
+    C = Z_users.size(1)
+    up, ldu = _lib.row_ptr(Z_users)
+    ip, ldi = _lib.row_ptr(Z_items)
+    u = torch.as_tensor(users, dtype=torch.int64).to(dev).contiguous()
+    p = torch.as_tensor(pos, dtype=torch.int64).to(dev).contiguous()
+    if u.shape != p.shape or u.dim() != 1:
+        raise ValueError("full_rank: users and pos must be 1-D and of equal length")
+    if sampler is not None and (sampler.n_users != Z_users.size(0) or sampler.n_items != Z_items.size(0)):
+        raise ValueError("full_rank: the sampler's history is over other users / items than the tables")
+    n = u.numel()
+    rank = torch.empty(n, dtype=torch.int32, device=dev)
+    ties = torch.empty(n, dtype=torch.int32, device=dev) if return_ties else None
+    ws, nbytes = _lib.workspace(lib.ppgat_full_rank_workspace_bytes, n, Z_items.size(0), C, device=dev)
+    _lib.check(lib.ppgat_full_rank(up, ldu, Z_users.size(0), ip, ldi, Z_items.size(0), C, _lib.ptr(u) if n else None,
+                                   _lib.ptr(p) if n else None, n,
+                                   None if sampler is None else sampler.ptr.data_ptr(),
+                                   None if sampler is None else sampler.items.data_ptr(),
+                                   rank.data_ptr() if n else None, _lib.ptr(ties) if n else None,
+                                   ws.data_ptr() if nbytes else None, nbytes, _lib.stream_handle(dev)), "full_rank")
+    if return_ties:
+        return rank.cpu().numpy(), ties.cpu().numpy()
+    return rank.cpu().numpy()
+
+
+def eval_full(model, cfg, item_feats: torch.Tensor, edge_index: torch.Tensor,
+              train_pos_idx: Dict[int, np.ndarray], eval_pos: Dict[int, int], Ks=(10, 20), sampler=None):
+    """eval_sampled's call shape and returned dict, under the full-ranking protocol: each held-out
+    positive is ranked against every item outside the user's train history (``full_rank``).
+    ``sampler``: a sampler.BPRSampler over the train lists; None builds one from
+    ``train_pos_idx``.  ``cfg`` is unused (no negatives are drawn)."""
+    with torch.no_grad():
+        Z = model(item_feats, edge_index)
+    if not eval_pos:
+        return metrics_from_ranks(np.zeros(0, np.int64), Ks)
+    n_users, n_items = model.n_users, model.n_items
+    if sampler is None:
+        from . import sampler as sampler_mod
+        from .train import user_csr
+        ptr, flat = user_csr(train_pos_idx, n_users)
+        sampler = sampler_mod.BPRSampler(ptr, flat, n_items, device=Z.device)
+    users = np.fromiter(eval_pos.keys(), np.int64, len(eval_pos))
+    pos = np.fromiter(eval_pos.values(), np.int64, len(eval_pos))
+    ranks = full_rank(Z[:n_users], Z[n_users:n_users + n_items], users, pos, sampler=sampler)
     return metrics_from_ranks(ranks, Ks)
 
 

@@ -189,6 +189,18 @@ def user_csr(train_pos_idx: Dict[int, np.ndarray], n_users: int):
     return ptr, flat
 
 
+FULL_EVAL_NOTE = ("Evaluation ranks the held-out positive against every item outside the user's train history "
+                  "(full ranking, no sampled negatives).")
+
+
+def evaluate(args, model, cfg, item_feats, edge_index, tr, eval_pos, dev_sampler, seed):
+    """One evaluation under --eval-mode: the reference's sampled protocol, or the full ranking."""
+    if args.eval_mode == "full":
+        return evaluation.eval_full(model, cfg, item_feats, edge_index, tr, eval_pos, sampler=dev_sampler)
+    return evaluation.eval_sampled(model, cfg, item_feats, edge_index, tr, eval_pos, fast=args.fast_eval,
+                                   sampler=dev_sampler if args.device_eval else None, seed=seed)
+
+
 def main_lightgcn(args):
     """train_lightgcn.py main(): the mini-batch loop over every positive x neg_per_pos
     (:313-336), sampled evaluation each epoch, best-val checkpoint on ndcg@20, reload, test."""
@@ -200,6 +212,7 @@ def main_lightgcn(args):
                      eval_neg_k=args.eval_neg_k)
     if args.world_size > 1:
         raise NotImplementedError("--model-family lightgcn runs on one GPU")
+    full = args.eval_mode == "full"
     if args.deterministic:
         enable_determinism(cfg.seed)
     set_seed(cfg.seed)
@@ -244,8 +257,7 @@ def main_lightgcn(args):
         avg_loss = float(total.item()) / max(1, nb)
         print(f"[LGCN][Epoch {epoch}] train_bpr_loss={avg_loss:.4f}")
         model.eval()
-        val_metrics = evaluation.eval_sampled(model, cfg, None, None, tr, va, fast=args.fast_eval,
-                                              sampler=dev_sampler if args.device_eval else None, seed=cfg.seed + epoch)
+        val_metrics = evaluate(args, model, cfg, None, None, tr, va, dev_sampler, cfg.seed + epoch)
         print(f"[LGCN][Epoch {epoch}] val: {val_metrics}")
         if args.structured_logs:
             log_event("epoch_end", run_id=run_id, epoch=epoch, loss=avg_loss, val=val_metrics)
@@ -256,11 +268,13 @@ def main_lightgcn(args):
     ckpt = torch.load(best_path, map_location=device, weights_only=True)
     model.load_state_dict(ckpt["state_dict"])
     model.eval()
-    test_metrics = evaluation.eval_sampled(model, cfg, None, None, tr, te, fast=args.fast_eval,
-                                           sampler=dev_sampler if args.device_eval else None, seed=cfg.seed)
+    test_metrics = evaluate(args, model, cfg, None, None, tr, te, dev_sampler, cfg.seed)
     print(f"[LGCN] test: {test_metrics}")
     out = {"best_val_ndcg@20": float(best), "val": val_metrics, "test": test_metrics, "config": cfg.__dict__,
            "notes": "Evaluation uses sampled 1000 negatives/user."}
+    if full:
+        out["config"] = {**cfg.__dict__, "eval_mode": "full"}
+        out["notes"] = FULL_EVAL_NOTE
     with open(metrics_path, "w") as f:
         json.dump(out, f, indent=2)
     print(f"[LGCN] Complete. Wrote {best_path} and {metrics_path}")
@@ -299,7 +313,7 @@ def _init_distributed(args):
     return rank, world, device
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description="Train GAT (MI355X-native)")
     ap.add_argument("--project-id", default="local")
     ap.add_argument("--region", default="us-central1")
@@ -340,7 +354,17 @@ def main(argv=None):
                     help="torch.distributed backend (nccl = RCCL on ROCm; gloo only for tests)")
     ap.add_argument("--partition", choices=["auto", "replicated", "halo"], default="auto",
                     help="auto: users sharded / items replicated for U-I graphs, halo otherwise")
-    args = ap.parse_args(argv)
+    ap.add_argument("--eval-mode", choices=["sampled", "full"], default="sampled",
+                    help="sampled: the reference's 1 positive + --eval-neg-k negatives; full: the positive against "
+                         "every item outside the user's train history (ppgat_full_rank), one GPU")
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    full = args.eval_mode == "full"
+    if full and args.world_size > 1:
+        raise NotImplementedError("--eval-mode full runs on one GPU (the sharded trainers evaluate sampled)")
     if args.model_family == "lightgcn":
         return main_lightgcn(args)
     args.layers = 2 if args.layers is None else args.layers
@@ -411,7 +435,7 @@ def main(argv=None):
     best = -1.0
     val_metrics: Dict[str, float] = {}
     dev_sampler = None
-    if args.fast_sampler or args.device_eval:
+    if args.fast_sampler or args.device_eval or full:
         ptr, flat = user_csr(tr, n_users)
         dev_sampler = sampler_mod.BPRSampler(ptr, flat, n_items, device=device)
     for epoch in range(1, cfg.epochs + 1):
@@ -443,9 +467,7 @@ def main(argv=None):
         if lead:
             print(f"[{tag}][Epoch {epoch}] loss={loss_val:.4f} ({cfg.loss})")
         eval_model.eval()
-        val_metrics = evaluation.eval_sampled(eval_model, cfg, item_feats, edge_index, tr, va, fast=args.fast_eval,
-                                              sampler=dev_sampler if args.device_eval else None,
-                                              seed=cfg.seed + epoch)
+        val_metrics = evaluate(args, eval_model, cfg, item_feats, edge_index, tr, va, dev_sampler, cfg.seed + epoch)
         if lead:
             print(f"[{tag}][Epoch {epoch}] val: {val_metrics}")
         if args.structured_logs and lead:
@@ -466,13 +488,15 @@ def main(argv=None):
             ids = torch.as_tensor(sharded.dg.own_user_ids(), dtype=torch.int64, device=model.user_emb.weight.device)
             sharded.user_emb_local.copy_(model.user_emb.weight.index_select(0, ids))
     eval_model.eval()
-    test_metrics = evaluation.eval_sampled(eval_model, cfg, item_feats, edge_index, tr, te, fast=args.fast_eval,
-                                           sampler=dev_sampler if args.device_eval else None, seed=cfg.seed)
+    test_metrics = evaluate(args, eval_model, cfg, item_feats, edge_index, tr, te, dev_sampler, cfg.seed)
     if lead:
         print(f"[{tag}] test: {test_metrics}")
     out = {"best_val_ndcg@20": float(best), "val": val_metrics, "test": test_metrics, "config": cfg.__dict__,
            "notes": f"One-backward-per-epoch with S sampled BPR triples; features={cfg.item_features}; "
                     f"loss={cfg.loss}"}
+    if full:
+        out["config"] = {**cfg.__dict__, "eval_mode": "full"}
+        out["notes"] += "; " + FULL_EVAL_NOTE
     if world > 1:
         import torch.distributed as tdist
         tdist.destroy_process_group()
