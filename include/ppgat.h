@@ -510,6 +510,30 @@ int ppgat_full_rank(const float* user_rows, int64_t ld_user, int64_t n_users, co
                     const int64_t* user_ptr, const int32_t* items_sorted, int32_t* rank, int32_t* ties,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- full-catalogue top-K (recommendation) -------------------------------------------
+ * The recommender's output: for query b, with u = users[b] (users == NULL: query b is user b,
+ * n_query <= n_users) and s(i) = <user_rows[u], item_rows[i]>, the k best items outside
+ * history(u) under the total order (score descending, item index ascending):
+ *   out_idx [n_query, k] int32, out_score [n_query, k] fp32 (nullable), best first;
+ *   fewer than k eligible items: the tail is -1 / -inf.
+ * Exclusion is by index, with ppgat_full_rank's CSR (user_ptr / items_sorted of
+ * ppgat_bpr_sampler_prepare; both NULL = no history); duplicates in a history change nothing,
+ * an empty history is legal, users may repeat.  Rows and channels as in ppgat_full_rank; NaN
+ * scores are outside the contract.  1 <= k <= ppgat_full_topk_max_k() (128).
+ * ppgat_full_rank's product with a selection epilogue: the score matrix is never written, and a
+ * (user, item) score is bitwise the one ppgat_full_rank compares.  No float atomics: the lists are
+ * a function of the total order alone, so two calls give the same bits.  The workspace
+ * (ppgat_full_topk_workspace_bytes, sized for the current device: its CU count decides how the
+ * item range is split) holds the candidate buffers, 8-byte aligned.  n_query == 0 succeeds
+ * without a launch. */
+int ppgat_full_topk_max_k(void);
+int ppgat_full_topk_supported(int channels);
+int ppgat_full_topk_workspace_bytes(int64_t n_query, int64_t n_items, int channels, int k, size_t* bytes);
+int ppgat_full_topk(const float* user_rows, int64_t ld_user, int64_t n_users, const float* item_rows, int64_t ld_item,
+                    int64_t n_items, int channels, const int64_t* users, int64_t n_query, const int64_t* user_ptr,
+                    const int32_t* items_sorted, int k, int32_t* out_idx, float* out_score, void* workspace,
+                    size_t workspace_bytes, void* stream);
+
 /* ---- serving top-K ------------------------------------------------------------------
  * Replaces: RecommenderRuntime.top_k_for_user_items, serving/runtime.py:56-76 (numpy):
  *   user_vec = mean(item_vecs[history]); scores = item_vecs @ user_vec; scores[history] = -1e9;

@@ -111,6 +111,11 @@ SIGNATURES = {
     "ppgat_full_rank_workspace_bytes": (c_int, [c_i64, c_i64, c_int, ctypes.POINTER(c_sz)]),
     "ppgat_full_rank": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp,
                                 c_vp, c_vp, c_sz, c_vp]),
+    "ppgat_full_topk_max_k": (c_int, []),
+    "ppgat_full_topk_supported": (c_int, [c_int]),
+    "ppgat_full_topk_workspace_bytes": (c_int, [c_i64, c_i64, c_int, c_int, ctypes.POINTER(c_sz)]),
+    "ppgat_full_topk": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_int, c_vp, c_i64, c_vp, c_vp, c_int, c_vp,
+                                c_vp, c_vp, c_sz, c_vp]),
     "ppgat_serve_topk_workspace_bytes": (c_int, [c_i64, c_int, c_int, ctypes.POINTER(c_sz)]),
     "ppgat_serve_topk": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "ppgat_fusion_fwd": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_int,

@@ -1013,6 +1013,72 @@ int ppgat_full_rank(const float* user_rows, int64_t ld_user, int64_t n_users, co
   return PPGAT_OK;
 }
 
+int ppgat_full_topk_max_k(void) { return ppgat::full_topk_max_k(); }
+
+int ppgat_full_topk_supported(int channels) { return ppgat::full_topk_channels_ok(channels) ? 1 : 0; }
+
+int ppgat_full_topk_workspace_bytes(int64_t n_query, int64_t n_items, int channels, int k, size_t* bytes) {
+  if (!bytes || n_query < 0 || n_items < 1 || n_items >= (int64_t)1 << 31)
+    return fail(PPGAT_ERR_INVALID, "full_topk_workspace_bytes: bad arguments");
+  if (!ppgat::full_topk_channels_ok(channels))
+    return fail(PPGAT_ERR_UNSUPPORTED, "full_topk_workspace_bytes: channels must be 32, 64, 128 or 256");
+  if (k < 1 || k > ppgat::full_topk_max_k()) return fail(PPGAT_ERR_INVALID, "full_topk_workspace_bytes: 1 <= k <= max_k");
+  hipError_t e = ppgat::full_topk_workspace(n_query, n_items, channels, k, bytes);
+  if (e != hipSuccess) return hip_fail(e, "full_topk_workspace_bytes");
+  return PPGAT_OK;
+}
+
+int ppgat_full_topk(const float* user_rows, int64_t ld_user, int64_t n_users, const float* item_rows, int64_t ld_item,
+                    int64_t n_items, int channels, const int64_t* users, int64_t n_query, const int64_t* user_ptr,
+                    const int32_t* items_sorted, int k, int32_t* out_idx, float* out_score, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+  if (!ppgat::full_topk_channels_ok(channels))
+    return fail(PPGAT_ERR_UNSUPPORTED, "full_topk: channels must be 32, 64, 128 or 256");
+  if (k < 1 || k > ppgat::full_topk_max_k()) return fail(PPGAT_ERR_INVALID, "full_topk: 1 <= k <= ppgat_full_topk_max_k()");
+  if (n_users < 1 || n_items < 1 || n_query < 0) return fail(PPGAT_ERR_INVALID, "full_topk: bad sizes");
+  if (n_items >= (int64_t)1 << 31 || n_query >= (int64_t)1 << 31)
+    return fail(PPGAT_ERR_UNSUPPORTED, "full_topk: n_items and n_query must be < 2^31");
+  if (ld_user < channels || ld_item < channels || (ld_user & 3) || (ld_item & 3))
+    return fail(PPGAT_ERR_INVALID, "full_topk: ld_user and ld_item must be >= channels and multiples of 4");
+  if (!user_rows || !item_rows || (n_query > 0 && !out_idx)) return fail(PPGAT_ERR_INVALID, "full_topk: null pointer");
+  if ((reinterpret_cast<uintptr_t>(user_rows) | reinterpret_cast<uintptr_t>(item_rows)) & 15)
+    return fail(PPGAT_ERR_INVALID, "full_topk: rows must be 16-byte aligned");
+  if ((user_ptr == nullptr) != (items_sorted == nullptr))
+    return fail(PPGAT_ERR_INVALID, "full_topk: user_ptr and items_sorted go together (both NULL = no history)");
+  if (!users && n_query > n_users)
+    return fail(PPGAT_ERR_INVALID, "full_topk: users == NULL means query b is user b, so n_query <= n_users");
+  if (n_query == 0) return PPGAT_OK;
+  // the workspace holds at least the unsplit plan's buffers on any device
+  if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 7) ||
+      workspace_bytes < ppgat::full_topk_workspace_floor(n_query, n_items, channels, k))
+    return fail(PPGAT_ERR_INVALID, "full_topk: workspace too small (ppgat_full_topk_workspace_bytes) or misaligned");
+  size_t need = 0;
+  hipError_t e = ppgat::full_topk_workspace(n_query, n_items, channels, k, &need);
+  if (e != hipSuccess) return hip_fail(e, "full_topk: device query");
+  if (workspace_bytes < need) return fail(PPGAT_ERR_INVALID, "full_topk: workspace too small (ppgat_full_topk_workspace_bytes)");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (users)
+    if (int rc = debug_range(users, 8, n_query, 0, n_users, "full_topk: users", st)) return rc;
+#if PPGAT_DEBUG
+  if (user_ptr) {  // the CSR's length lives on the device: user_ptr[n_users]
+    int64_t nnz = 0;
+    hipError_t he = hipMemcpyAsync(&nnz, user_ptr + n_users, sizeof(int64_t), hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess) he = hipStreamSynchronize(st);
+    if (he != hipSuccess) return hip_fail(he, "full_topk: user_ptr");
+    if (nnz < 0) return fail(PPGAT_ERR_INVALID, "full_topk: user_ptr ends below 0");
+    if (int rc = debug_range(user_ptr, 8, n_users + 1, 0, nnz + 1, "full_topk: user_ptr", st)) return rc;
+    if (int rc = debug_range(items_sorted, 4, nnz, 0, n_items, "full_topk: items_sorted", st)) return rc;
+  }
+#endif
+  e = ppgat::full_topk(user_rows, ld_user, n_users, item_rows, ld_item, n_items, channels, users, n_query, user_ptr,
+                       items_sorted, k, out_idx, out_score, workspace, workspace_bytes, st);
+#if PPGAT_DEBUG
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+#endif
+  if (e != hipSuccess) return hip_fail(e, "full_topk");
+  return PPGAT_OK;
+}
+
 int ppgat_serve_topk_workspace_bytes(int64_t n_items, int channels, int n_users, size_t* bytes) {
   if (!bytes || n_items < 1 || n_users < 0) return fail(PPGAT_ERR_INVALID, "serve_topk_workspace_bytes: bad sizes");
   if (channels != 64 && channels != 128 && channels != 256) return fail(PPGAT_ERR_UNSUPPORTED, "serve_topk: channels");

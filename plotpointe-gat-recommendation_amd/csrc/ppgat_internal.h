@@ -185,6 +185,18 @@ hipError_t full_rank(const float* U, int64_t ldu, int64_t n_users, const float* 
                      const int64_t* users, const int64_t* pos, int64_t n_eval, const int64_t* uptr,
                      const int32_t* hist, int32_t* rank, int32_t* ties, hipStream_t st);
 
+// full-catalogue top-K (ppgat_fulltopk.hip): the k best items outside history(users[b]) under
+// (score descending, item ascending); users nullable (query b = user b), uptr / hist nullable
+// together, out_score nullable.  The workspace depends on the device's CU count (the item range is
+// split to fill the chip); _floor is its device-independent lower bound (no split).
+bool full_topk_channels_ok(int C);
+int full_topk_max_k();
+size_t full_topk_workspace_floor(int64_t n_query, int64_t n_items, int C, int k);
+hipError_t full_topk_workspace(int64_t n_query, int64_t n_items, int C, int k, size_t* bytes);
+hipError_t full_topk(const float* U, int64_t ldu, int64_t n_users, const float* I, int64_t ldi, int64_t n_items, int C,
+                     const int64_t* users, int64_t n_query, const int64_t* uptr, const int32_t* hist, int k,
+                     int32_t* out_idx, float* out_score, void* ws, size_t ws_bytes, hipStream_t st);
+
 // fusion MLP (ppgat_fusion.hip)
 bool fusion_shape_ok(int Dt, int Di, int h1, int d_out);
 size_t fusion_workspace_bytes(int Dt, int Di);

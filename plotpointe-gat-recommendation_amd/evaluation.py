@@ -14,6 +14,10 @@
   held-out positive against EVERY item outside the user's train history (no sampling, so the
   metrics are exact and comparable with published ones).  One fused matrix-core pass
   (``ppgat_full_rank``): the ``[users, items]`` score matrix is never written.
+* ``recommend_topk`` / ``topk_metrics`` / ``eval_topk`` -- the recommender's output: for every
+  user the K best items outside the train history, from the same fused product with a selection
+  epilogue (``ppgat_full_topk``), and the metrics that need the lists (several held-out items
+  per user, precision, catalogue coverage).
 * ``export_item_embeddings`` -- tools/export_item_embeddings.py:139-145.
 * ``top_k_for_user_items`` / ``top_k_batch`` -- serving/runtime.py:56-76 on the device
   (``ppgat_serve_topk``): user vector = mean of history rows, history masked to -1e9,
@@ -183,6 +187,135 @@ def eval_full(model, cfg, item_feats: torch.Tensor, edge_index: torch.Tensor,
     pos = np.fromiter(eval_pos.values(), np.int64, len(eval_pos))
     ranks = full_rank(Z[:n_users], Z[n_users:n_users + n_items], users, pos, sampler=sampler)
     return metrics_from_ranks(ranks, Ks)
+
+
+def recommend_topk(Z_users: torch.Tensor, Z_items: torch.Tensor, users=None, k: int = 20, sampler=None,
+                   return_scores: bool = True):
+    """The recommender's output: for each query user the ``k`` best items outside the user's train
+    history, best first under the total order (score descending, item index ascending), scores
+    s(i) = <Z_users[u], Z_items[i]> -- bitwise the scores ``full_rank`` compares.
+
+    Returns device tensors ``(idx [n, k] int32, scores [n, k] fp32)`` (``idx`` alone with
+    ``return_scores=False``); a user with fewer than ``k`` eligible items has the tail -1 / -inf.
+    ``users``: the query users (may repeat); None = every user of ``Z_users`` in order.  Tables
+    and ``sampler`` as in ``full_rank``: row or column views of one node table are used in place,
+    the sampler's sorted history CSR is the excluded set (None = nothing is excluded).  One fused
+    matrix-core pass (``ppgat_full_topk``): the ``[users, items]`` score matrix is never written."""
+    lib = _lib.load()
+    for t in (Z_users, Z_items):
+        if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2:
+            raise RuntimeError("recommend_topk: 2-D fp32 ROCm tensors required (no CPU path)")
+    if Z_users.size(1) != Z_items.size(1) or Z_users.device != Z_items.device:
+        raise ValueError("recommend_topk: Z_users and Z_items differ in width or device")
+    dev = Z_users.device
+    C = Z_users.size(1)
+    up, ldu = _lib.row_ptr(Z_users)
+    ip, ldi = _lib.row_ptr(Z_items)
+    u = None
+    if users is not None:
+        u = torch.as_tensor(users, dtype=torch.int64).to(dev).contiguous()
+        if u.dim() != 1:
+            raise ValueError("recommend_topk: users must be 1-D")
+    if sampler is not None and (sampler.n_users != Z_users.size(0) or sampler.n_items != Z_items.size(0)):
+        raise ValueError("recommend_topk: the sampler's history is over other users / items than the tables")
+    n = Z_users.size(0) if u is None else u.numel()
+    k = int(k)
+    idx = torch.empty(n, k, dtype=torch.int32, device=dev)
+    sc = torch.empty(n, k, dtype=torch.float32, device=dev) if return_scores else None
+    ws, nbytes = _lib.workspace(lib.ppgat_full_topk_workspace_bytes, n, Z_items.size(0), C, k, device=dev)
+    _lib.check(lib.ppgat_full_topk(up, ldu, Z_users.size(0), ip, ldi, Z_items.size(0), C,
+                                   _lib.ptr(u) if n else None, n,
+                                   None if sampler is None else sampler.ptr.data_ptr(),
+                                   None if sampler is None else sampler.items.data_ptr(), k,
+                                   idx.data_ptr() if n else None, _lib.ptr(sc) if n else None,
+                                   ws.data_ptr() if nbytes else None, nbytes, _lib.stream_handle(dev)), "full_topk")
+    return (idx, sc) if return_scores else idx
+
+
+def _held_out_csr(held_out, n: int):
+    """(ptr int64 [n + 1], items int64) from a (ptr, items) CSR or a list with one int or one
+    sequence of held-out items per query."""
+    if isinstance(held_out, tuple) and len(held_out) == 2:
+        ptr, items = np.asarray(held_out[0], np.int64), np.asarray(held_out[1], np.int64)
+    else:
+        rows = [np.atleast_1d(np.asarray(h, np.int64)) for h in held_out]
+        ptr = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+        items = np.concatenate(rows) if rows else np.zeros(0, np.int64)
+    if len(ptr) != n + 1 or (len(ptr) and ptr[-1] != len(items)):
+        raise ValueError("topk_metrics: held_out must have one entry per row of idx")
+    return ptr, items
+
+
+def topk_metrics(idx, held_out, n_items: int, Ks: Sequence[int] = (10, 20)) -> Dict[str, float]:
+    """List metrics of top-K recommendations (host numpy).  ``idx`` [n, k]: ``recommend_topk``'s
+    lists (-1 = no item); ``held_out``: per query one held-out item or several (a list of ints /
+    sequences, or a ``(ptr, items)`` CSR).  Means over the queries with at least one held-out item:
+
+    * ``recall@K``    hits / |held out|  (the LightGCN papers' Recall@K)
+    * ``ndcg@K``      DCG / IDCG, IDCG over min(|held out|, K) items
+    * ``precision@K`` hits / K
+    * ``hit@K``       1 if any held-out item is in the first K
+    * ``coverage@K``  distinct items in the first K of all lists / n_items
+
+    With one held-out item per query, ``recall@K`` and ``ndcg@K`` are ``metrics_from_ranks``'
+    values for rank = position + 1."""
+    if isinstance(idx, torch.Tensor):
+        idx = idx.cpu().numpy()
+    idx = np.asarray(idx, np.int64)
+    if idx.ndim != 2:
+        raise ValueError("topk_metrics: idx must be [n, k]")
+    n, kmax = idx.shape
+    if any(K < 1 or K > kmax for K in Ks):
+        raise ValueError(f"topk_metrics: every K must be in [1, {kmax}] (the lists' length)")
+    ptr, items = _held_out_csr(held_out, n)
+    lens = np.diff(ptr)
+    rows = np.repeat(np.arange(n, dtype=np.int64), lens)
+    keys = np.unique(rows * n_items + items)  # duplicates in a held-out set count once
+    lens = np.bincount(keys // n_items, minlength=n) if n else lens
+    hits = (idx >= 0) & np.isin(np.arange(n, dtype=np.int64)[:, None] * n_items + idx, keys)
+    have = lens > 0
+    disc = np.array([1.0 / math.log2(q + 2) for q in range(kmax)])
+    idcg = np.concatenate([[0.0], np.cumsum(disc)])
+    out = {}
+    per = {}
+    for K in Ks:
+        h = hits[have, :K]
+        nh = h.sum(1)
+        m = lens[have]
+        per[f"recall@{K}"] = nh / m
+        per[f"ndcg@{K}"] = (h * disc[:K]).sum(1) / idcg[np.minimum(m, K)]
+        per[f"precision@{K}"] = nh / float(K)
+        per[f"hit@{K}"] = (nh > 0).astype(np.float64)
+    for name in ("recall", "ndcg", "precision", "hit"):
+        for K in Ks:
+            v = per[f"{name}@{K}"]
+            out[f"{name}@{K}"] = float(np.mean(v)) if len(v) else 0.0
+    for K in Ks:
+        top = idx[:, :K]
+        out[f"coverage@{K}"] = float(len(np.unique(top[top >= 0]))) / float(n_items)
+    return out
+
+
+def eval_topk(model, cfg, item_feats: torch.Tensor, edge_index: torch.Tensor,
+              train_pos_idx: Dict[int, np.ndarray], eval_pos: Dict[int, object], Ks=(10, 20), sampler=None):
+    """``eval_full``'s call shape with the metrics that need the lists: the model's forward, the
+    max(Ks) best items outside each evaluated user's train history (``recommend_topk``), and
+    ``topk_metrics`` against the held-out items.  ``eval_pos`` values: one item or a sequence of
+    items per user.  ``cfg`` is unused."""
+    with torch.no_grad():
+        Z = model(item_feats, edge_index)
+    n_users, n_items = model.n_users, model.n_items
+    if not eval_pos:
+        return topk_metrics(np.zeros((0, max(Ks)), np.int64), [], n_items, Ks)
+    if sampler is None:
+        from . import sampler as sampler_mod
+        from .train import user_csr
+        ptr, flat = user_csr(train_pos_idx, n_users)
+        sampler = sampler_mod.BPRSampler(ptr, flat, n_items, device=Z.device)
+    users = np.fromiter(eval_pos.keys(), np.int64, len(eval_pos))
+    idx = recommend_topk(Z[:n_users], Z[n_users:n_users + n_items], users, k=max(Ks), sampler=sampler,
+                         return_scores=False)
+    return topk_metrics(idx, list(eval_pos.values()), n_items, Ks)
 
 
 def export_item_embeddings(model, item_feats: torch.Tensor, edge_index: torch.Tensor) -> np.ndarray:

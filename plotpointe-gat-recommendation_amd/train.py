@@ -201,6 +201,48 @@ def evaluate(args, model, cfg, item_feats, edge_index, tr, eval_pos, dev_sampler
                                    sampler=dev_sampler if args.device_eval else None, seed=seed)
 
 
+def raw_id_maps(cfg: Config, synthetic: Optional[str], n_users: int, n_items: int):
+    """(user_ids [n_users], item_ids [n_items]): the raw id of each node index, from the node maps
+    load_inputs read (config 2's synthetic graph has no raw ids: the indices themselves)."""
+    if synthetic == "cfg2":
+        return np.arange(n_users).astype(str), np.arange(n_items).astype(str)
+    if synthetic:
+        maps = data.node_maps_from_interactions(data.synthetic_interactions_small(seed=0))
+    else:
+        with open(_local(cfg.graphs_prefix) / "node_maps.json") as f:
+            maps = json.load(f)
+    u2i, i2i = data.index_maps(maps)
+    user_ids, item_ids = np.full(n_users, "", dtype=object), np.full(n_items, "", dtype=object)
+    for raw, idx in u2i.items():
+        user_ids[idx] = raw
+    for raw, idx in i2i.items():
+        item_ids[idx] = raw
+    return user_ids.astype(str), item_ids.astype(str)
+
+
+def write_recommendations(args, cfg: Config, model, item_feats, edge_index, tr, n_users: int, n_items: int,
+                          dev_sampler, device):
+    """--recommend-out: the --recommend-k best items outside each user's train history for EVERY
+    user (evaluation.recommend_topk on the model's final embeddings), written as an .npz with
+    ``users`` [n_users], ``items`` [n_users, K] (-1 = fewer than K eligible), ``scores`` and the
+    raw ids ``user_ids`` / ``item_ids``.  Returns the run record's "recommendations" entry."""
+    if dev_sampler is None:
+        ptr, flat = user_csr(tr, n_users)
+        dev_sampler = sampler_mod.BPRSampler(ptr, flat, n_items, device=device)
+    with torch.no_grad():
+        Z = model(item_feats, edge_index)
+    k = int(args.recommend_k)
+    idx, sc = evaluation.recommend_topk(Z[:n_users], Z[n_users:n_users + n_items], None, k=k, sampler=dev_sampler)
+    idx, sc = idx.cpu().numpy(), sc.cpu().numpy()
+    user_ids, item_ids = raw_id_maps(cfg, args.synthetic, n_users, n_items)
+    path = Path(args.recommend_out)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "wb") as f:
+        np.savez(f, users=np.arange(n_users, dtype=np.int64), items=idx, scores=sc, user_ids=user_ids,
+                 item_ids=item_ids)
+    return {"path": str(path), "k": k, f"coverage@{k}": float(len(np.unique(idx[idx >= 0]))) / float(n_items)}
+
+
 def main_lightgcn(args):
     """train_lightgcn.py main(): the mini-batch loop over every positive x neg_per_pos
     (:313-336), sampled evaluation each epoch, best-val checkpoint on ndcg@20, reload, test."""
@@ -275,6 +317,9 @@ def main_lightgcn(args):
     if full:
         out["config"] = {**cfg.__dict__, "eval_mode": "full"}
         out["notes"] = FULL_EVAL_NOTE
+    if args.recommend_out:
+        out["recommendations"] = write_recommendations(args, cfg, model, None, None, tr, n_users, n_items,
+                                                       dev_sampler, device)
     with open(metrics_path, "w") as f:
         json.dump(out, f, indent=2)
     print(f"[LGCN] Complete. Wrote {best_path} and {metrics_path}")
@@ -357,11 +402,18 @@ def build_parser():
     ap.add_argument("--eval-mode", choices=["sampled", "full"], default="sampled",
                     help="sampled: the reference's 1 positive + --eval-neg-k negatives; full: the positive against "
                          "every item outside the user's train history (ppgat_full_rank), one GPU")
+    ap.add_argument("--recommend-out", default=None, metavar="PATH",
+                    help="after the test evaluation, write every user's --recommend-k best items outside the train "
+                         "history (ppgat_full_topk) to this .npz; one GPU")
+    ap.add_argument("--recommend-k", type=int, default=20)
     return ap
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.recommend_out and args.world_size > 1:
+        raise NotImplementedError("--recommend-out runs on one GPU (--world-size 1): the lists are made from the "
+                                  "whole user and item tables")
     full = args.eval_mode == "full"
     if full and args.world_size > 1:
         raise NotImplementedError("--eval-mode full runs on one GPU (the sharded trainers evaluate sampled)")
@@ -497,6 +549,9 @@ def main(argv=None):
     if full:
         out["config"] = {**cfg.__dict__, "eval_mode": "full"}
         out["notes"] += "; " + FULL_EVAL_NOTE
+    if args.recommend_out:  # one GPU (refused above otherwise)
+        out["recommendations"] = write_recommendations(args, cfg, model, item_feats, edge_index, tr, n_users, n_items,
+                                                       dev_sampler, device)
     if world > 1:
         import torch.distributed as tdist
         tdist.destroy_process_group()
