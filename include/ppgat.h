@@ -465,6 +465,50 @@ int ppgat_lgcn_hop(const ppgat_schedule* sched, const int32_t* col, const float*
                    const float* acc0, const float* acc1, int64_t acc_split, float div, float* out, float* accw,
                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- GATv2 dynamic-attention layer ----------------------------------------------------------
+ * Replaces: torch_geometric.nn.GATv2Conv (Brody et al., "How Attentive are Graph Attention
+ *   Networks?") with concat=False, add_self_loops=False, edge_dim=None, residual=False, after
+ *   its projections x_l = lin_l(x), x_r = lin_r(x) (both [N, H, C]; x_r may be x_l's buffer,
+ *   share_weights).  Per edge j -> i and head h:
+ *     t_ij  = x_l[j] + x_r[i];   e_ij = sum_c att[h,c] * leaky_relu(t_ij[c], negative_slope)
+ *     alpha = exp(e_ij - max_i) / (sum over the in-edges of i of exp(e - max_i) + 1e-16)
+ *     out_i = mean_h sum_j mask_ij alpha_ij x_l[j] + bias     (no in-edges: exactly bias)
+ *   mask is ppgat_fwd's counter-hash dropout multiplier of (effective seed, original edge
+ *   column, head, dropout_p).  The C entries carry "dynatt" in their names (the symbol check of
+ *   this header admits lower-case letters and underscores only).
+ * ppgat_dynatt_supported: 1 for (heads, channels) in {(1,32), (1,64), (1,128), (2,64), (2,128),
+ *   (4,64), (4,128)}; every other shape returns PPGAT_ERR_UNSUPPORTED before any device work.
+ * ppgat_dynatt_workspace_bytes: backward == 0: the forward's hub-piece states (n_dst_hub_items
+ *   of the CSR schedule); backward != 0: node state, dbias / datt partial rows and the hub
+ *   pieces' partial sums and rows of the passes.  Host only.
+ * ppgat_dynatt_fwd: dst_sched over the CSR by destination.  Writes out [N,C], m and inv_l =
+ *   1/(l + 1e-16) [N,H] (saved for the backward).  seed_used (device uint64[1]) is required
+ *   when dropout_p > 0 and receives the effective seed (seed folded with the dropout epoch),
+ *   which the kernels read from there.
+ * ppgat_dynatt_bwd: src_sched over the CSC by source, dst_sched over the CSR by destination.
+ *   Given grad_out [N,C] returns grad_x_l and grad_x_r [N,H,C] (two buffers even when x_r is
+ *   x_l: the caller adds them), grad_att [H,C] and, when grad_bias != NULL, grad_bias [C].  A
+ *   sweep by destination sums D_i = sum_j alpha_ij dalpha_ij edge by edge (not g_i . agg_i: the
+ *   softmax backward's cancellation is then exact for a single in-edge), one pass by source
+ *   owns grad_x_l[j], one by destination owns grad_x_r[i] and recomputes the logit gradient from
+ *   grad_out[i] . x_l[j]; grad_att and grad_bias are per-block partial rows summed in block
+ *   order.  No float atomics: two calls give the same bits.  seed_used: the forward's (required
+ *   when dropout_p > 0), so the backward regenerates the forward's mask.  No entry synchronises
+ *   the host. */
+int ppgat_dynatt_supported(int heads, int channels);
+int ppgat_dynatt_workspace_bytes(int64_t n_nodes, int64_t n_dst_hub_items, int64_t n_src_hub_items, int heads,
+                                 int channels, int backward, size_t* bytes);
+int ppgat_dynatt_fwd(const ppgat_schedule* dst_sched, const int32_t* col, const int32_t* csr_eid, int64_t n_nodes,
+                     int64_t n_edges, int heads, int channels, const float* x_l, const float* x_r, const float* att,
+                     const float* bias, float negative_slope, float dropout_p, uint64_t seed, uint64_t* seed_used,
+                     float* out, float* m, float* inv_l, void* workspace, size_t workspace_bytes, void* stream);
+int ppgat_dynatt_bwd(const ppgat_schedule* src_sched, const ppgat_schedule* dst_sched, const int32_t* row,
+                     const int32_t* csc_eid, const int32_t* col, const int32_t* csr_eid, int64_t n_nodes,
+                     int64_t n_edges, int heads, int channels, const float* x_l, const float* x_r, const float* att,
+                     const float* m, const float* inv_l, const float* grad_out, float negative_slope,
+                     float dropout_p, const uint64_t* seed_used, float* grad_x_l, float* grad_x_r, float* grad_att,
+                     float* grad_bias, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- sampled-evaluation candidates ---------------------------------------------------
  * Replaces: the candidate draw of eval_sampled, scripts/train_gat_pyg.py:157-167 (a Python
  *   loop over ~192k users: np.random.randint(0, n_items) redrawn while the item is in the

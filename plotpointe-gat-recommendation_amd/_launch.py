@@ -108,6 +108,37 @@ def rows_return_add(dst, ret, ret_ptr, pos, cols: int):
                                        stream_handle(dst.device)), "rows_return_add")
 
 
+# the GATv2 dynamic-attention layer (ppgat_dynatt_*); ``g``: a hip_ops.CSRGraph
+def dynatt_supported(heads: int, channels: int) -> bool:
+    return bool(load().ppgat_dynatt_supported(int(heads), int(channels)))
+
+
+def dynatt_workspace(g, heads: int, channels: int, backward: bool, dev):
+    return workspace(load().ppgat_dynatt_workspace_bytes, g.n_nodes, g.fwd_sched.n_hub_items,
+                     g.bwd_sched.n_hub_items, heads, channels, 1 if backward else 0, device=dev, floor=1)
+
+
+def dynatt_fwd(g, xl, xr, att, bias, heads: int, channels: int, slope, p, seed, seed_buf, out, m, inv_l):
+    lib, dev, E = load(), xl.device, g.n_edges
+    ws, nbytes = dynatt_workspace(g, heads, channels, False, dev)
+    check(lib.ppgat_dynatt_fwd(_sched(g.fwd_sched), *edge_ptrs(E, g.col, g.csr_eid), g.n_nodes, E, heads, channels,
+                               ptr(xl), ptr(xr), ptr(att), ptr(bias), float(slope), float(p), seed64(seed),
+                               ptr(seed_buf), ptr(out), ptr(m), ptr(inv_l), ptr(ws), nbytes, stream_handle(dev)),
+          "gatv2_fwd")
+
+
+def dynatt_bwd(g, xl, xr, att, m, inv_l, grad_out, heads: int, channels: int, slope, p, seed_buf, dxl, dxr, datt,
+               dbias):
+    lib, dev, E = load(), xl.device, g.n_edges
+    ws, nbytes = dynatt_workspace(g, heads, channels, True, dev)
+    check(lib.ppgat_dynatt_bwd(_sched(g.bwd_sched), _sched(g.fwd_sched), *edge_ptrs(E, g.row, g.csc_eid, g.col,
+                                                                                    g.csr_eid),
+                               g.n_nodes, E, heads, channels, ptr(xl), ptr(xr), ptr(att), ptr(m), ptr(inv_l),
+                               ptr(grad_out), float(slope), float(p), ptr(seed_buf), ptr(dxl), ptr(dxr), ptr(datt),
+                               ptr(dbias), ptr(ws), nbytes, stream_handle(dev)),
+          "gatv2_bwd")
+
+
 # the aggregate-then-transform layer (ppgat_xgat_*); ``v``: a hip_ops.XViews
 def xgat_weights(W, a_s, a_d, H: int, C: int, A=None, Wt=None, Wg=None):
     """Whichever of A [2, H, K] (needs a_s, a_d), Wt [H * K, C] and Wg [C, H * K] are given."""

@@ -105,6 +105,12 @@ SIGNATURES = {
     "ppgat_lgcn_hop_workspace_bytes": (c_int, [c_i64, c_int, ctypes.POINTER(c_sz)]),
     "ppgat_lgcn_hop": (c_int, [SP, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_f,
                                c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "ppgat_dynatt_supported": (c_int, [c_int, c_int]),
+    "ppgat_dynatt_workspace_bytes": (c_int, [c_i64, c_i64, c_i64, c_int, c_int, c_int, ctypes.POINTER(c_sz)]),
+    "ppgat_dynatt_fwd": (c_int, [SP, c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_f, c_f, c_u64,
+                                 c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "ppgat_dynatt_bwd": (c_int, [SP, SP, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp,
+                                 c_vp, c_vp, c_f, c_f, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "ppgat_eval_sample": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_u64, c_vp, c_vp, c_vp]),
     "ppgat_sampled_rank": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "ppgat_full_rank_supported": (c_int, [c_int]),

@@ -6,13 +6,17 @@
                       ``forward(x, edge_index)``, and state_dict keys
                       (``lin.weight`` [H*C, F], ``att_src``/``att_dst`` [1, H, C],
                       ``bias`` [C]; the older ``lin_src.weight``/``lin_dst.weight`` keys load too).
+``GATv2Conv``      -- torch_geometric.nn.GATv2Conv (dynamic attention) under the same options,
+                      PyG's constructor names and state_dict keys (``att``, ``lin_l.*``,
+                      ``lin_r.*``, ``bias``); runs as ``hip_ops.gatv2_aggregate`` after two
+                      ``hip_ops.linear`` projections.
 ``SimpleGATLayer`` -- scripts/train_gat_custom.py:63-93, same constructor
                       ``(in_dim, out_dim, attn_dropout=0.1)``, same parameter creation
                       order (so a seeded construction yields the reference's weights)
                       and keys (``lin.weight``, ``a_src``, ``a_dst``).
 
-Both run the layer as ``hip_ops.gat_layer``, entirely in ``libppgat.so``: ``h = lin(x)``
-on the fp32 matrix cores with the node attention terms in the GEMM epilogue, the fused
+``GATConv`` and ``SimpleGATLayer`` run the layer as ``hip_ops.gat_layer``, entirely in
+``libppgat.so``: ``h = lin(x)`` on the fp32 matrix cores with the node attention terms in the GEMM epilogue, the fused
 edge kernels, and a backward that folds the attention terms into the projection GEMMs;
 multi-head layers wider than their input (config 5) run aggregate-then-transform
 (``hip_ops.GATLayerX``: x_j gathered once per edge, one transform GEMM).  Dropout on alpha is the counter-hash mask of
@@ -25,7 +29,7 @@ import math
 import torch
 
 from . import _lib
-from .hip_ops import gat_layer, graph_cache
+from .hip_ops import gat_layer, gatv2_aggregate, gatv2_supported, graph_cache, join_rows, linear
 
 
 def _dropout_seed() -> int:
@@ -108,6 +112,76 @@ class GATConv(torch.nn.Module):
     def __repr__(self):
         return (f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, heads={self.heads}, "
                 f"backend=hip)")
+
+
+class GATv2Conv(torch.nn.Module):
+    """MI355X-native ``torch_geometric.nn.GATv2Conv`` (dynamic attention, Brody et al.) with the
+    options ``GATConv`` above supports: ``e_ij = att . leaky_relu(lin_l(x)_j + lin_r(x)_i)``,
+    softmax per destination, dropout on alpha, head mean, bias.  PyG's constructor names and
+    defaults, and its state_dict keys (``att`` [1, H, C], ``lin_l.weight`` [H*C, F],
+    ``lin_l.bias`` [H*C], ``lin_r.*`` -- the same module as ``lin_l`` with ``share_weights`` --
+    and ``bias`` [C]).  The projections run through ``hip_ops.linear``, the rest in the fused
+    kernels of ``hip_ops.gatv2_aggregate``."""
+
+    def __init__(self, in_channels: int, out_channels: int, heads: int = 1, concat: bool = True,
+                 negative_slope: float = 0.2, dropout: float = 0.0, add_self_loops: bool = True,
+                 edge_dim=None, fill_value="mean", bias: bool = True, share_weights: bool = False,
+                 residual: bool = False, **kwargs):
+        super().__init__()
+        if isinstance(in_channels, (tuple, list)):
+            raise NotImplementedError("bipartite (tuple) in_channels not implemented")
+        if concat:
+            raise NotImplementedError("GATv2Conv(concat=True) not implemented; pass concat=False")
+        if add_self_loops:
+            raise NotImplementedError("GATv2Conv(add_self_loops=True) not implemented; pass False")
+        if edge_dim is not None:
+            raise NotImplementedError("edge_dim (edge features) not implemented")
+        if residual:
+            raise NotImplementedError("residual=True not implemented")
+        if not gatv2_supported(int(heads), int(out_channels)):
+            raise NotImplementedError(f"GATv2Conv(heads={heads}, out_channels={out_channels}) not implemented: "
+                                      "(H, C) in (1,32) (1,64) (1,128) (2,64) (2,128) (4,64) (4,128)")
+        self.in_channels, self.out_channels, self.heads = in_channels, out_channels, heads
+        self.concat, self.negative_slope, self.dropout = concat, negative_slope, dropout
+        self.add_self_loops, self.edge_dim, self.fill_value = add_self_loops, edge_dim, fill_value
+        self.share_weights, self.residual = share_weights, residual
+        self.lin_l = torch.nn.Linear(in_channels, heads * out_channels, bias=bias)
+        self.lin_r = self.lin_l if share_weights else torch.nn.Linear(in_channels, heads * out_channels, bias=bias)
+        self.att = torch.nn.Parameter(torch.empty(1, heads, out_channels))
+        self.bias = torch.nn.Parameter(torch.empty(out_channels)) if bias else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for lin in (self.lin_l,) if self.share_weights else (self.lin_l, self.lin_r):
+            _glorot_(lin.weight)
+            if lin.bias is not None:
+                torch.nn.init.zeros_(lin.bias)
+        _glorot_(self.att)
+        if self.bias is not None:
+            torch.nn.init.zeros_(self.bias)
+
+    def _aggregate(self, x: torch.Tensor, edge_index: torch.Tensor) -> torch.Tensor:
+        graph = graph_cache.get(edge_index, x.size(0))
+        p = float(self.dropout) if self.training else 0.0
+        seed = _dropout_seed() if p > 0 else 0
+        xl = linear(x, self.lin_l.weight, self.lin_l.bias)
+        xr = xl if self.share_weights else linear(x, self.lin_r.weight, self.lin_r.bias)
+        return gatv2_aggregate(xl, xr, self.att, self.bias, graph, self.heads, self.out_channels,
+                               float(self.negative_slope), p, seed)
+
+    def forward(self, x: torch.Tensor, edge_index: torch.Tensor, return_attention_weights=None) -> torch.Tensor:
+        if return_attention_weights:
+            raise NotImplementedError("return_attention_weights not implemented")
+        return self._aggregate(x, edge_index)
+
+    def forward_segments(self, x: torch.Tensor, x_items: torch.Tensor, edge_index: torch.Tensor) -> torch.Tensor:
+        """forward(cat(x, x_items), edge_index); the two blocks are joined without a copy when they
+        lie back to back (the model's node table), else concatenated."""
+        return self._aggregate(join_rows(x, x_items), edge_index)
+
+    def __repr__(self):
+        return (f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, heads={self.heads}, "
+                f"share_weights={self.share_weights}, backend=hip)")
 
 
 class SimpleGATLayer(torch.nn.Module):

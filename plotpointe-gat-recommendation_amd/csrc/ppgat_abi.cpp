@@ -932,6 +932,105 @@ int ppgat_lgcn_hop(const ppgat_schedule* sched, const int32_t* col, const float*
   return PPGAT_OK;
 }
 
+// ---- GATv2 dynamic-attention layer ----------------------------------------------------
+int ppgat_dynatt_supported(int heads, int channels) { return ppgat::gatv2_shape_ok(heads, channels) ? 1 : 0; }
+
+static int dynatt_check(int heads, int channels, float p, const char* who) {
+  if (!ppgat::gatv2_shape_ok(heads, channels))
+    return fail(PPGAT_ERR_UNSUPPORTED, std::string(who) + ": (heads, channels) must be one of (1,32) (1,64) (1,128) "
+                                                          "(2,64) (2,128) (4,64) (4,128)");
+  if (!(p >= 0.f && p < 1.f)) return fail(PPGAT_ERR_INVALID, std::string(who) + ": dropout p must be in [0, 1)");
+  return PPGAT_OK;
+}
+
+int ppgat_dynatt_workspace_bytes(int64_t n_nodes, int64_t n_dst_hub_items, int64_t n_src_hub_items, int heads,
+                                 int channels, int backward, size_t* bytes) {
+  if (!bytes || n_nodes < 0 || n_dst_hub_items < 0 || n_src_hub_items < 0)
+    return fail(PPGAT_ERR_INVALID, "dynatt_workspace_bytes: bad arguments");
+  if (int rc = dynatt_check(heads, channels, 0.f, "dynatt_workspace_bytes")) return rc;
+  *bytes = backward ? ppgat::gatv2_bwd_workspace_bytes(n_nodes, n_src_hub_items, n_dst_hub_items, heads, channels)
+                    : ppgat::gatv2_fwd_workspace_bytes(n_dst_hub_items, heads, channels);
+  return PPGAT_OK;
+}
+
+static int dynatt_check_edges(const ppgat_schedule* s, const int32_t* idx, int64_t n_nodes, int64_t n_edges,
+                              const char* who, hipStream_t st) {
+  if (int rc = debug_range(idx, 4, n_edges, 0, n_nodes, who, st)) return rc;
+  if (int rc = debug_range(s->item_row, 4, s->n_items, 0, n_nodes, who, st)) return rc;
+  return debug_range(s->item_end, 4, s->n_items, 0, n_edges + 1, who, st);
+}
+
+int ppgat_dynatt_fwd(const ppgat_schedule* dst_sched, const int32_t* col, const int32_t* csr_eid, int64_t n_nodes,
+                     int64_t n_edges, int heads, int channels, const float* x_l, const float* x_r, const float* att,
+                     const float* bias, float negative_slope, float dropout_p, uint64_t seed, uint64_t* seed_used,
+                     float* out, float* m, float* inv_l, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = dynatt_check(heads, channels, dropout_p, "dynatt_fwd")) return rc;
+  if (n_nodes < 0 || n_edges < 0) return fail(PPGAT_ERR_INVALID, "dynatt_fwd: bad sizes");
+  if (n_nodes >= (int64_t)1 << 31 || n_edges >= (int64_t)1 << 31)
+    return fail(PPGAT_ERR_UNSUPPORTED, "dynatt_fwd: nodes and edges must be < 2^31");
+  if (int rc = check_sched(dst_sched, n_nodes, "dynatt_fwd")) return rc;
+  if (n_nodes > 0 && (!x_l || !x_r || !att || !out || !m || !inv_l))
+    return fail(PPGAT_ERR_INVALID, "dynatt_fwd: null pointer");
+  if (n_edges > 0 && !col) return fail(PPGAT_ERR_INVALID, "dynatt_fwd: null col");
+  if (dropout_p > 0.f && (!seed_used || (n_edges > 0 && !csr_eid)))
+    return fail(PPGAT_ERR_INVALID, "dynatt_fwd: dropout needs seed_used and csr_eid");
+  if (dst_sched->n_hub_items > 0 &&
+      (!workspace || workspace_bytes < ppgat::gatv2_fwd_workspace_bytes(dst_sched->n_hub_items, heads, channels)))
+    return fail(PPGAT_ERR_INVALID, "dynatt_fwd: workspace too small");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = dynatt_check_edges(dst_sched, col, n_nodes, n_edges, "dynatt_fwd: index", st)) return rc;
+  const ppgat::ItemsArg it{dst_sched->item_row, dst_sched->item_beg, dst_sched->item_end, dst_sched->n_items,
+                           dst_sched->n_hub_items, dst_sched->n_long_items};
+  Timed t(PPGAT_K_FWD, st);
+  hipError_t e = hipSuccess;
+  if (dropout_p > 0.f) e = ppgat::seed_snapshot(seed, seed_used, st);
+  if (e == hipSuccess)
+    e = ppgat::gatv2_fwd(it, col, csr_eid, heads, channels, x_l, x_r, att, bias, negative_slope, dropout_p, seed_used,
+                         out, m, inv_l, static_cast<float*>(workspace), dst_sched->hub_row, dst_sched->hub_ptr,
+                         dst_sched->n_hubs, st);
+  if (e != hipSuccess) return hip_fail(e, "dynatt_fwd");
+  return PPGAT_OK;
+}
+
+int ppgat_dynatt_bwd(const ppgat_schedule* src_sched, const ppgat_schedule* dst_sched, const int32_t* row,
+                     const int32_t* csc_eid, const int32_t* col, const int32_t* csr_eid, int64_t n_nodes,
+                     int64_t n_edges, int heads, int channels, const float* x_l, const float* x_r, const float* att,
+                     const float* m, const float* inv_l, const float* grad_out, float negative_slope,
+                     float dropout_p, const uint64_t* seed_used, float* grad_x_l, float* grad_x_r, float* grad_att,
+                     float* grad_bias, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = dynatt_check(heads, channels, dropout_p, "dynatt_bwd")) return rc;
+  if (n_nodes < 0 || n_edges < 0) return fail(PPGAT_ERR_INVALID, "dynatt_bwd: bad sizes");
+  if (n_nodes >= (int64_t)1 << 31 || n_edges >= (int64_t)1 << 31)
+    return fail(PPGAT_ERR_UNSUPPORTED, "dynatt_bwd: nodes and edges must be < 2^31");
+  if (int rc = check_sched(src_sched, n_nodes, "dynatt_bwd (source schedule)")) return rc;
+  if (int rc = check_sched(dst_sched, n_nodes, "dynatt_bwd (destination schedule)")) return rc;
+  if (!att || !grad_att || (n_nodes > 0 && (!x_l || !x_r || !m || !inv_l || !grad_out || !grad_x_l || !grad_x_r)))
+    return fail(PPGAT_ERR_INVALID, "dynatt_bwd: null pointer");
+  if (grad_x_l == grad_x_r && n_nodes > 0)
+    return fail(PPGAT_ERR_INVALID, "dynatt_bwd: grad_x_l and grad_x_r must be two buffers");
+  if (n_edges > 0 && (!row || !col)) return fail(PPGAT_ERR_INVALID, "dynatt_bwd: null row or col");
+  if (dropout_p > 0.f && (!seed_used || (n_edges > 0 && (!csc_eid || !csr_eid))))
+    return fail(PPGAT_ERR_INVALID, "dynatt_bwd: dropout needs seed_used, csc_eid and csr_eid");
+  if (!workspace || workspace_bytes < ppgat::gatv2_bwd_workspace_bytes(n_nodes, src_sched->n_hub_items,
+                                                                       dst_sched->n_hub_items, heads, channels))
+    return fail(PPGAT_ERR_INVALID, "dynatt_bwd: workspace too small");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = dynatt_check_edges(src_sched, row, n_nodes, n_edges, "dynatt_bwd: source index", st)) return rc;
+  if (int rc = dynatt_check_edges(dst_sched, col, n_nodes, n_edges, "dynatt_bwd: destination index", st)) return rc;
+  const ppgat::ItemsArg si{src_sched->item_row, src_sched->item_beg, src_sched->item_end, src_sched->n_items,
+                           src_sched->n_hub_items, src_sched->n_long_items};
+  const ppgat::ItemsArg di{dst_sched->item_row, dst_sched->item_beg, dst_sched->item_end, dst_sched->n_items,
+                           dst_sched->n_hub_items, dst_sched->n_long_items};
+  Timed t(PPGAT_K_BWD_SRC, st);
+  hipError_t e = ppgat::gatv2_bwd(si, src_sched->hub_row, src_sched->hub_ptr, src_sched->n_hubs, di,
+                                  dst_sched->hub_row, dst_sched->hub_ptr, dst_sched->n_hubs, row, csc_eid, col,
+                                  csr_eid, n_nodes, heads, channels, x_l, x_r, att, m, inv_l, grad_out,
+                                  negative_slope, dropout_p, seed_used, grad_x_l, grad_x_r, grad_att, grad_bias,
+                                  workspace, st);
+  if (e != hipSuccess) return hip_fail(e, "dynatt_bwd");
+  return PPGAT_OK;
+}
+
 int ppgat_eval_sample(const int64_t* user_ptr, const int32_t* items_sorted, const int64_t* users, const int64_t* pos,
                       int64_t n_eval, int64_t n_neg, int64_t n_items, uint64_t seed, int64_t* cands, int32_t* bad,
                       void* stream) {

@@ -166,6 +166,22 @@ hipError_t lgcn_hop(const ItemsArg& it, const int32_t* col, const float* val, in
                     float div, float* out, float* accw, float* partial, const int32_t* hub_row,
                     const int32_t* hub_ptr, int64_t n_hubs, hipStream_t st);
 
+// GATv2 dynamic-attention layer (ppgat_gatv2.hip); seed: the device slot holding the effective
+// mask seed (read when p > 0)
+bool gatv2_shape_ok(int H, int C);
+size_t gatv2_fwd_workspace_bytes(int64_t n_hub_items, int H, int C);
+size_t gatv2_bwd_workspace_bytes(int64_t n, int64_t src_hub_items, int64_t dst_hub_items, int H, int C);
+hipError_t gatv2_fwd(const ItemsArg& it, const int32_t* col, const int32_t* eid, int H, int C, const float* xl,
+                     const float* xr, const float* att, const float* bias, float slope, float p,
+                     const uint64_t* seed, float* out, float* m, float* invl, float* partial,
+                     const int32_t* hub_row, const int32_t* hub_ptr, int64_t n_hubs, hipStream_t st);
+hipError_t gatv2_bwd(const ItemsArg& src, const int32_t* src_hub_row, const int32_t* src_hub_ptr, int64_t src_hubs,
+                     const ItemsArg& dst, const int32_t* dst_hub_row, const int32_t* dst_hub_ptr, int64_t dst_hubs,
+                     const int32_t* row, const int32_t* csc_eid, const int32_t* col, const int32_t* csr_eid,
+                     int64_t n, int H, int C, const float* xl, const float* xr, const float* att, const float* m,
+                     const float* invl, const float* g, float slope, float p, const uint64_t* seed, float* dxl,
+                     float* dxr, float* datt, float* dbias, void* ws, hipStream_t st);
+
 hipError_t eval_sample(const int64_t* ptr, const int32_t* items_sorted, const int64_t* users, const int64_t* pos,
                        int64_t n_eval, int64_t n_neg, int64_t n_items, uint64_t seed, int64_t* cands, int32_t* bad,
                        hipStream_t st);

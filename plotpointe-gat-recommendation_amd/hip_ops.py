@@ -368,6 +368,81 @@ def gat_aggregate(h, att_src, att_dst, bias, graph, heads, channels, mode, slope
     return GATAggregate.apply(h, att_src, att_dst, bias, graph, heads, channels, mode, slope, dropout_p, seed)
 
 
+# ---------------------------------------------------------------------------
+# GATv2 dynamic attention (ppgat_dynatt_*)
+# ---------------------------------------------------------------------------
+def gatv2_supported(heads: int, channels: int) -> bool:
+    """ppgat_dynatt_supported: the (heads, channels) the fused GATv2 kernels are built for."""
+    return _launch.dynatt_supported(heads, channels)
+
+
+def _gatv2_require_shape(heads: int, channels: int):
+    if not gatv2_supported(heads, channels):
+        raise NotImplementedError(f"GATv2 (heads={heads}, channels={channels}) not implemented: (H, C) in "
+                                  "(1,32) (1,64) (1,128) (2,64) (2,128) (4,64) (4,128)")
+
+
+class GATv2Aggregate(torch.autograd.Function):
+    """x_l, x_r [N, H*C] -> out [N, C]: the fused dynamic-attention softmax-aggregate and its
+    atomic-free backward (a D sweep, one pass by source for dx_l, one by destination for dx_r, datt).
+    ``x_r`` may be ``x_l`` itself (share_weights): autograd then adds the two row gradients."""
+
+    @staticmethod
+    def forward(ctx, xl, xr, att, bias, graph: CSRGraph, heads: int, channels: int, slope: float, dropout_p: float,
+                seed: int):
+        N, dev = graph.n_nodes, xl.device
+        shared = xr is xl or (xr.data_ptr() == xl.data_ptr() and xr.stride() == xl.stride())
+        xl = xl.contiguous()
+        xr = xl if shared else xr.contiguous()
+        att_c = att.detach().contiguous().view(heads, channels)
+        bias_c = bias.detach().contiguous() if bias is not None else None
+        need_grad = any(ctx.needs_input_grad[:4])
+        ctx.seed_buf = seed_buffer(dropout_p, dev)
+        out, m, inv_l, _ = _fwd_outputs(N, heads, channels, False, dev)
+        _launch.dynatt_fwd(graph, xl, xr, att_c, bias_c, heads, channels, slope, dropout_p, seed, ctx.seed_buf, out, m,
+                           inv_l)
+        if need_grad:
+            ctx.save_for_backward(xl, xr, att_c, m, inv_l)
+        ctx.graph = graph
+        ctx.meta = (heads, channels, slope, dropout_p, bias is not None)
+        ctx.att_shape = att.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        xl, xr, att, m, inv_l = ctx.saved_tensors
+        heads, channels, slope, p, has_bias = ctx.meta
+        grad_out = grad_out.contiguous()
+        _check_dev("grad_out", grad_out, torch.float32, xl.device)
+        dxl, dxr = torch.empty_like(xl), torch.empty_like(xl)
+        datt = torch.empty(heads, channels, dtype=torch.float32, device=xl.device)
+        dbias = torch.empty(channels, dtype=torch.float32, device=xl.device) \
+            if has_bias and ctx.needs_input_grad[3] else None
+        _launch.dynatt_bwd(ctx.graph, xl, xr, att, m, inv_l, grad_out, heads, channels, slope, p, ctx.seed_buf, dxl, dxr,
+                           datt, dbias)
+        return dxl, dxr, datt.view(ctx.att_shape), dbias, None, None, None, None, None, None
+
+
+def gatv2_aggregate(xl, xr, att, bias, graph, heads, channels, slope, dropout_p=0.0, seed=0):
+    """GATv2Conv after its projections: ``out_i = mean_h sum_j alpha_ij x_l[j] + bias`` with
+    ``alpha = softmax_i(att . leaky_relu(x_l[j] + x_r[i]))`` (include/ppgat.h ppgat_dynatt_fwd)."""
+    heads, channels = int(heads), int(channels)
+    for name, t in (("xl", xl), ("xr", xr), ("att", att)) + ((("bias", bias),) if bias is not None else ()):
+        _require(isinstance(t, torch.Tensor), f"{name}: expected a tensor")
+        _require(t.is_cuda, f"{name}: ppgat runs on ROCm devices only (got {t.device}); there is no CPU path")
+        _require(t.dtype == torch.float32, f"{name}: expected torch.float32, got {t.dtype}")
+        _require(t.device == xl.device, f"{name}: on {t.device}, expected {xl.device}")
+    _gatv2_require_shape(heads, channels)
+    N = graph.n_nodes
+    _require(xl.dim() == 2 and tuple(xl.shape) == (N, heads * channels),
+             f"xl must be [{N}, {heads * channels}], got {tuple(xl.shape)}")
+    _require(tuple(xr.shape) == tuple(xl.shape), "xr must have xl's shape")
+    _require(att.numel() == heads * channels, "att must be [H, C]")
+    _require(bias is None or bias.numel() == channels, "bias must be [C]")
+    _require(0.0 <= float(dropout_p) < 1.0, "dropout p must be in [0, 1)")
+    return GATv2Aggregate.apply(xl, xr, att, bias, graph, heads, channels, float(slope), float(dropout_p), int(seed))
+
+
 def _bwd_edges_src(g: CSRGraph, sched: Schedule, r0: int, h, s_src, nstate, grad_out, D, S, dz, heads, channels,
                    mode, slope, p, seed, seed_buf=None):
     """Pass B over the source rows of ``sched`` (row ids relative to r0; edge slots and

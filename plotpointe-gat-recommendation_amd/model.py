@@ -3,6 +3,7 @@ as the reference so checkpoints ({"state_dict", "config"}) load both ways:
 
 ``PyGGAT``    -- scripts/train_gat_pyg.py:68-88  (user_emb, item_proj, convs.{l})
 ``CustomGAT`` -- scripts/train_gat_custom.py:96-115 (user_emb, item_proj, layers.{l})
+``PyGGATv2``  -- PyGGAT with ``GATv2Conv`` layers (dynamic attention); no reference script
 
 node_features = cat(user_emb.weight, item_proj(item_feats)); L stacked layers with no
 nonlinearity in between (train_gat_pyg.py:86-87).  forward() hands the two row blocks to
@@ -19,7 +20,7 @@ import os
 import torch
 
 from . import hip_ops
-from .conv import GATConv, SimpleGATLayer
+from .conv import GATConv, GATv2Conv, SimpleGATLayer
 
 
 def node_table(model: torch.nn.Module, n_items: int) -> torch.Tensor:
@@ -100,6 +101,32 @@ class PyGGAT(torch.nn.Module):
         for _ in range(layers):
             self.convs.append(GATConv(hidden, hidden, heads=heads, dropout=attn_dropout, add_self_loops=False,
                                       concat=False))
+        self._register_state_dict_hook(_unalias_state)
+
+    def node_features(self, item_feats: torch.Tensor) -> torch.Tensor:
+        u = self.user_emb.weight
+        v = hip_ops.linear(item_feats, self.item_proj.weight, self.item_proj.bias)
+        return torch.cat([u, v], dim=0)
+
+    def forward(self, item_feats: torch.Tensor, edge_index: torch.Tensor) -> torch.Tensor:
+        return _stack(self, self.item_proj, item_feats, self.convs, edge_index)
+
+
+class PyGGATv2(torch.nn.Module):
+    """``PyGGAT`` with GATv2's dynamic attention: the same user_emb / item_proj / convs.{l}
+    structure, each conv a ``GATv2Conv(hidden, hidden, heads, concat=False, add_self_loops=False)``."""
+
+    def __init__(self, n_users: int, n_items: int, item_feat_dim: int, hidden: int, layers: int, heads: int,
+                 attn_dropout: float, share_weights: bool = False):
+        super().__init__()
+        self.n_users, self.n_items = n_users, n_items
+        self.user_emb = torch.nn.Embedding(n_users, hidden)
+        torch.nn.init.normal_(self.user_emb.weight, std=0.1)
+        self.item_proj = torch.nn.Linear(item_feat_dim, hidden)
+        self.convs = torch.nn.ModuleList()
+        for _ in range(layers):
+            self.convs.append(GATv2Conv(hidden, hidden, heads=heads, dropout=attn_dropout, add_self_loops=False,
+                                        concat=False, share_weights=share_weights))
         self._register_state_dict_hook(_unalias_state)
 
     def node_features(self, item_feats: torch.Tensor) -> torch.Tensor:

@@ -97,6 +97,7 @@ class Config:
     item_features: str = "fused"
     loss: str = "bpr"
     model_family: str = "gat_pyg"
+    share_weights: bool = False  # gatv2_pyg: lin_r is lin_l
 
 
 @dataclass
@@ -155,6 +156,9 @@ def build_model(cfg: Config, n_users: int, n_items: int, feat_dim: int):
     if cfg.model_family == "gat_pyg":
         return model_mod.PyGGAT(n_users, n_items, item_feat_dim=feat_dim, hidden=cfg.hidden_dim, layers=cfg.layers,
                                 heads=cfg.heads, attn_dropout=cfg.attn_dropout)
+    if cfg.model_family == "gatv2_pyg":
+        return model_mod.PyGGATv2(n_users, n_items, item_feat_dim=feat_dim, hidden=cfg.hidden_dim, layers=cfg.layers,
+                                  heads=cfg.heads, attn_dropout=cfg.attn_dropout, share_weights=cfg.share_weights)
     m = model_mod.CustomGAT(n_users, n_items, item_feat_dim=feat_dim, hidden=cfg.hidden_dim, layers=cfg.layers)
     for layer in m.layers:
         layer.drop.p = cfg.attn_dropout
@@ -366,7 +370,9 @@ def build_parser():
     ap.add_argument("--graphs-prefix", default="data/graphs")
     ap.add_argument("--embeddings-prefix", default="data/embeddings")
     ap.add_argument("--models-prefix", default="models/gat")
-    ap.add_argument("--model-family", choices=["gat_pyg", "gat_custom", "lightgcn"], default="gat_pyg")
+    ap.add_argument("--model-family", choices=["gat_pyg", "gat_custom", "lightgcn", "gatv2_pyg"], default="gat_pyg",
+                    help="gatv2_pyg: PyGGAT with GATv2Conv layers (dynamic attention), one GPU")
+    ap.add_argument("--share-weights", action="store_true", help="gatv2_pyg: GATv2Conv(share_weights=True)")
     ap.add_argument("--hidden-dim", type=int, default=128)
     ap.add_argument("--layers", type=int, default=None, help="default 2 (GAT), 3 (lightgcn)")
     ap.add_argument("--heads", type=int, default=1)
@@ -417,6 +423,8 @@ def main(argv=None):
     full = args.eval_mode == "full"
     if full and args.world_size > 1:
         raise NotImplementedError("--eval-mode full runs on one GPU (the sharded trainers evaluate sampled)")
+    if args.model_family == "gatv2_pyg" and args.world_size > 1:
+        raise NotImplementedError("--model-family gatv2_pyg runs on one GPU (the sharded model is PyGGAT)")
     if args.model_family == "lightgcn":
         return main_lightgcn(args)
     args.layers = 2 if args.layers is None else args.layers
@@ -426,7 +434,7 @@ def main(argv=None):
                  models_prefix=args.models_prefix, hidden_dim=args.hidden_dim, layers=args.layers, heads=args.heads,
                  attn_dropout=args.attn_dropout, epochs=args.epochs, samples_per_epoch=args.samples_per_epoch,
                  seed=args.seed, eval_neg_k=args.eval_neg_k, item_features=args.item_features, loss=args.loss,
-                 model_family=args.model_family)
+                 model_family=args.model_family, share_weights=args.share_weights)
     if args.lr is not None:
         cfg.lr = args.lr
     if args.l2 is not None:
@@ -442,7 +450,7 @@ def main(argv=None):
             raise NotImplementedError("--world-size > 1: the sharded model is PyGGAT (--model-family gat_pyg)")
         rank, world, device = _init_distributed(args)
     lead = rank == 0
-    tag = "GAT-PYG" if cfg.model_family == "gat_pyg" else "GAT-CUSTOM"
+    tag = {"gat_pyg": "GAT-PYG", "gatv2_pyg": "GATV2-PYG"}.get(cfg.model_family, "GAT-CUSTOM")
     run_id = f"{cfg.model_family}_d{cfg.hidden_dim}_{int(time.time())}"
     if world > 1:  # one run id (checkpoint / metrics names) for every rank: rank 0's
         import torch.distributed as tdist
