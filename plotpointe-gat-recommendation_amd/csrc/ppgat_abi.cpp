@@ -243,13 +243,10 @@ int ppgat_fwd(const ppgat_schedule* sched, const int32_t* col, const int32_t* cs
     return fail(PPGAT_ERR_INVALID, "fwd: workspace too small");
   const float eps = mode == PPGAT_MODE_PYG ? 1e-16f : 1e-9f;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const ppgat::ItemsArg it{sched->item_row, sched->item_beg, sched->item_end, sched->n_items, sched->n_hub_items,
-                           sched->n_long_items};
   Timed t(PPGAT_K_FWD, st);
-  hipError_t e = ppgat::launch_fwd(it, col, csr_eid, heads, channels, h, s_src, s_dst, bias, mode, negative_slope,
+  hipError_t e = ppgat::launch_fwd(*sched, col, csr_eid, heads, channels, h, s_src, s_dst, bias, mode, negative_slope,
                                    eps, dropout_p, seed, dropout_p > 0.f ? seed_used : nullptr, out, m, inv_l, agg,
-                                   static_cast<float*>(workspace),
-                                   sched->hub_row, sched->hub_ptr, sched->n_hubs, st);
+                                   static_cast<float*>(workspace), st);
   if (e != hipSuccess) return hip_fail(e, "fwd");
   return PPGAT_OK;
 }
@@ -305,16 +302,12 @@ int ppgat_bwd_edges(const ppgat_schedule* src_sched, const int32_t* row, const i
     return fail(PPGAT_ERR_INVALID, "bwd_edges: workspace too small");
   const float gscale = mode == PPGAT_MODE_PYG ? 1.f / (float)heads : 1.f;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const ppgat::ItemsArg it{src_sched->item_row, src_sched->item_beg, src_sched->item_end, src_sched->n_items,
-                           src_sched->n_hub_items, src_sched->n_long_items};
   hipError_t e;
   {
     Timed t(PPGAT_K_BWD_SRC, st);
-    e = ppgat::launch_bwd_src(it, row, csc_eid, dz_slot, heads, channels, h, s_src, nstate, grad_out, mode,
-                              negative_slope, gscale, dropout_p, seed, seed_used, grad_h, ld_grad_h, ds_src,
-                              ld_ds_src, dz,
-                              static_cast<float*>(workspace), src_sched->hub_row, src_sched->hub_ptr,
-                              src_sched->n_hubs, st);
+    e = ppgat::launch_bwd_src(*src_sched, row, csc_eid, dz_slot, heads, channels, h, s_src, nstate, grad_out, mode,
+                              negative_slope, gscale, dropout_p, seed, seed_used, grad_h, ld_grad_h, ds_src, ld_ds_src,
+                              dz, static_cast<float*>(workspace), st);
   }
   if (e != hipSuccess) return hip_fail(e, "bwd_edges");
   return PPGAT_OK;
@@ -331,10 +324,8 @@ static int bwd_dst_sum_impl(const ppgat_schedule* fwd_sched, int64_t n_nodes, in
     return fail(PPGAT_ERR_INVALID, "bwd_dst_sum: workspace too small");
   hipStream_t st = static_cast<hipStream_t>(stream);
   Timed t(PPGAT_K_BWD_EPI, st);
-  const ppgat::ItemsArg it{fwd_sched->item_row, fwd_sched->item_beg, fwd_sched->item_end, fwd_sched->n_items,
-                           fwd_sched->n_hub_items, fwd_sched->n_long_items};
-  hipError_t e = ppgat::launch_dst_sum(it, heads, dz, csr2csc, ds_dst, ld_ds_dst, static_cast<float*>(workspace),
-                                       fwd_sched->hub_row, fwd_sched->hub_ptr, fwd_sched->n_hubs, st);
+  hipError_t e = ppgat::launch_dst_sum(*fwd_sched, heads, dz, csr2csc, ds_dst, ld_ds_dst,
+                                       static_cast<float*>(workspace), st);
   if (e != hipSuccess) return hip_fail(e, "bwd_dst_sum");
   return PPGAT_OK;
 }
@@ -923,11 +914,9 @@ int ppgat_lgcn_hop(const ppgat_schedule* sched, const int32_t* col, const float*
   if (int rc = debug_range(col, 4, n_edges, 0, n_src, "lgcn_hop: col", st)) return rc;
   if (int rc = debug_range(sched->item_row, 4, sched->n_items, 0, n_rows, "lgcn_hop: item_row", st)) return rc;
   if (int rc = debug_range(sched->item_end, 4, sched->n_items, 0, n_edges + 1, "lgcn_hop: item_end", st)) return rc;
-  const ppgat::ItemsArg it{sched->item_row, sched->item_beg, sched->item_end, sched->n_items, sched->n_hub_items,
-                           sched->n_long_items};
   Timed t(PPGAT_K_FWD, st);
-  hipError_t e = ppgat::lgcn_hop(it, col, val, channels, src0, src1, src_split, acc0, acc1, acc_split, div, out, accw,
-                                 static_cast<float*>(workspace), sched->hub_row, sched->hub_ptr, sched->n_hubs, st);
+  hipError_t e = ppgat::lgcn_hop(*sched, col, val, channels, src0, src1, src_split, acc0, acc1, acc_split, div, out,
+                                 accw, static_cast<float*>(workspace), st);
   if (e != hipSuccess) return hip_fail(e, "lgcn_hop");
   return PPGAT_OK;
 }
@@ -979,15 +968,12 @@ int ppgat_dynatt_fwd(const ppgat_schedule* dst_sched, const int32_t* col, const 
     return fail(PPGAT_ERR_INVALID, "dynatt_fwd: workspace too small");
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (int rc = dynatt_check_edges(dst_sched, col, n_nodes, n_edges, "dynatt_fwd: index", st)) return rc;
-  const ppgat::ItemsArg it{dst_sched->item_row, dst_sched->item_beg, dst_sched->item_end, dst_sched->n_items,
-                           dst_sched->n_hub_items, dst_sched->n_long_items};
   Timed t(PPGAT_K_FWD, st);
   hipError_t e = hipSuccess;
   if (dropout_p > 0.f) e = ppgat::seed_snapshot(seed, seed_used, st);
   if (e == hipSuccess)
-    e = ppgat::gatv2_fwd(it, col, csr_eid, heads, channels, x_l, x_r, att, bias, negative_slope, dropout_p, seed_used,
-                         out, m, inv_l, static_cast<float*>(workspace), dst_sched->hub_row, dst_sched->hub_ptr,
-                         dst_sched->n_hubs, st);
+    e = ppgat::gatv2_fwd(*dst_sched, col, csr_eid, heads, channels, x_l, x_r, att, bias, negative_slope, dropout_p,
+                         seed_used, out, m, inv_l, static_cast<float*>(workspace), st);
   if (e != hipSuccess) return hip_fail(e, "dynatt_fwd");
   return PPGAT_OK;
 }
@@ -1017,16 +1003,10 @@ int ppgat_dynatt_bwd(const ppgat_schedule* src_sched, const ppgat_schedule* dst_
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (int rc = dynatt_check_edges(src_sched, row, n_nodes, n_edges, "dynatt_bwd: source index", st)) return rc;
   if (int rc = dynatt_check_edges(dst_sched, col, n_nodes, n_edges, "dynatt_bwd: destination index", st)) return rc;
-  const ppgat::ItemsArg si{src_sched->item_row, src_sched->item_beg, src_sched->item_end, src_sched->n_items,
-                           src_sched->n_hub_items, src_sched->n_long_items};
-  const ppgat::ItemsArg di{dst_sched->item_row, dst_sched->item_beg, dst_sched->item_end, dst_sched->n_items,
-                           dst_sched->n_hub_items, dst_sched->n_long_items};
   Timed t(PPGAT_K_BWD_SRC, st);
-  hipError_t e = ppgat::gatv2_bwd(si, src_sched->hub_row, src_sched->hub_ptr, src_sched->n_hubs, di,
-                                  dst_sched->hub_row, dst_sched->hub_ptr, dst_sched->n_hubs, row, csc_eid, col,
-                                  csr_eid, n_nodes, heads, channels, x_l, x_r, att, m, inv_l, grad_out,
-                                  negative_slope, dropout_p, seed_used, grad_x_l, grad_x_r, grad_att, grad_bias,
-                                  workspace, st);
+  hipError_t e = ppgat::gatv2_bwd(*src_sched, *dst_sched, row, csc_eid, col, csr_eid, n_nodes, heads, channels, x_l,
+                                  x_r, att, m, inv_l, grad_out, negative_slope, dropout_p, seed_used, grad_x_l,
+                                  grad_x_r, grad_att, grad_bias, workspace, st);
   if (e != hipSuccess) return hip_fail(e, "dynatt_bwd");
   return PPGAT_OK;
 }
@@ -1532,15 +1512,12 @@ static int xgat_fwd_impl(const ppgat_schedule* dst_sched, const int32_t* col, co
       (!workspace || workspace_bytes < partial_bytes(dst_sched->n_hub_items, heads, in_channels)))
     return fail(PPGAT_ERR_INVALID, "xgat_fwd: workspace too small");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const ppgat::ItemsArg it{dst_sched->item_row, dst_sched->item_beg, dst_sched->item_end, dst_sched->n_items,
-                           dst_sched->n_hub_items, dst_sched->n_long_items};
   Timed t(PPGAT_K_FWD, st);
   hipError_t e = hipSuccess;
   if (dropout_p > 0.f) e = ppgat::seed_snapshot(seed, seed_used, st);
   if (e == hipSuccess)
-    e = ppgat::xgat_fwd(it, col, csr_eid, x, ldx, in_channels, heads, s_src, s_dst, negative_slope, dropout_p, seed,
-                        seed_used, agg, m, inv_l, static_cast<float*>(workspace), dst_sched->hub_row,
-                        dst_sched->hub_ptr, dst_sched->n_hubs, st, x_colmax_bits);
+    e = ppgat::xgat_fwd(*dst_sched, col, csr_eid, x, ldx, in_channels, heads, s_src, s_dst, negative_slope, dropout_p,
+                        seed, seed_used, agg, m, inv_l, static_cast<float*>(workspace), st, x_colmax_bits);
   if (e != hipSuccess) return hip_fail(e, "xgat_fwd");
   return PPGAT_OK;
 }
@@ -1606,13 +1583,10 @@ int ppgat_xgat_bwd_edges(const ppgat_schedule* src_sched, const int32_t* row, co
       (!workspace || workspace_bytes < partial_bytes(src_sched->n_hub_items, 1, in_channels)))
     return fail(PPGAT_ERR_INVALID, "xgat_bwd_edges: workspace too small");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const ppgat::ItemsArg it{src_sched->item_row, src_sched->item_beg, src_sched->item_end, src_sched->n_items,
-                           src_sched->n_hub_items, src_sched->n_long_items};
   Timed t(PPGAT_K_BWD_SRC, st);
-  hipError_t e = ppgat::xgat_bwd_edges(it, row, csc_eid, dz_slot, x, ldx, in_channels, heads, s_src, nstate, gt,
+  hipError_t e = ppgat::xgat_bwd_edges(*src_sched, row, csc_eid, dz_slot, x, ldx, in_channels, heads, s_src, nstate, gt,
                                        att_proj, negative_slope, dropout_p, seed, seed_used, dx, lddx, S, lds, dz,
-                                       static_cast<float*>(workspace), src_sched->hub_row, src_sched->hub_ptr,
-                                       src_sched->n_hubs, st);
+                                       static_cast<float*>(workspace), st);
   if (e != hipSuccess) return hip_fail(e, "xgat_bwd_edges");
   return PPGAT_OK;
 }
@@ -1642,13 +1616,10 @@ int ppgat_xgat_bwd_edges_g(const ppgat_schedule* src_sched, const int32_t* row, 
     return fail(PPGAT_ERR_INVALID, "xgat_bwd_edges_g: workspace too small");
   if (!al16(hs) || !al16(g) || !al16(acc)) return fail(PPGAT_ERR_UNSUPPORTED, "xgat_bwd_edges_g: 16-byte aligned rows");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const ppgat::ItemsArg it{src_sched->item_row, src_sched->item_beg, src_sched->item_end, src_sched->n_items,
-                           src_sched->n_hub_items, src_sched->n_long_items};
   Timed t(PPGAT_K_BWD_SRC, st);
-  hipError_t e = ppgat::xgat_bwd_edges_g(it, row, csc_eid, dz_slot, hs, channels, heads, s_src, nstate, g, ldg,
+  hipError_t e = ppgat::xgat_bwd_edges_g(*src_sched, row, csc_eid, dz_slot, hs, channels, heads, s_src, nstate, g, ldg,
                                          negative_slope, dropout_p, seed, seed_used, acc, S, lds, dz,
-                                         static_cast<float*>(workspace), src_sched->hub_row, src_sched->hub_ptr,
-                                         src_sched->n_hubs, st);
+                                         static_cast<float*>(workspace), st);
   if (e != hipSuccess) return hip_fail(e, "xgat_bwd_edges_g");
   return PPGAT_OK;
 }
@@ -1672,13 +1643,10 @@ static int xgat_bwd_edges_gd_impl(const ppgat_schedule* src_sched, const int32_t
     return fail(PPGAT_ERR_INVALID, "xgat_bwd_edges_gd: workspace too small");
   if (!al16(hs) || !al16(g) || !al16(acc)) return fail(PPGAT_ERR_UNSUPPORTED, "xgat_bwd_edges_gd: 16-byte aligned rows");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const ppgat::ItemsArg it{src_sched->item_row, src_sched->item_beg, src_sched->item_end, src_sched->n_items,
-                           src_sched->n_hub_items, src_sched->n_long_items};
   Timed t(PPGAT_K_BWD_SRC, st);
-  hipError_t e = ppgat::xgat_bwd_edges_g(it, row, csc_eid, dz_slot, hs, channels, heads, s_src, nstate, g, ldg,
+  hipError_t e = ppgat::xgat_bwd_edges_g(*src_sched, row, csc_eid, dz_slot, hs, channels, heads, s_src, nstate, g, ldg,
                                          negative_slope, dropout_p, seed, seed_used, acc, nullptr, 0, dalpha,
-                                         static_cast<float*>(workspace), src_sched->hub_row, src_sched->hub_ptr,
-                                         src_sched->n_hubs, st, pdalpha, g_colmax_bits);
+                                         static_cast<float*>(workspace), st, pdalpha, g_colmax_bits);
   if (e != hipSuccess) return hip_fail(e, "xgat_bwd_edges_gd");
   return PPGAT_OK;
 }
@@ -1750,12 +1718,9 @@ int ppgat_xgat_bwd_dz(const ppgat_schedule* src_sched, const int32_t* row, const
   if (src_sched->n_hub_items > 0 && (!workspace || workspace_bytes < (size_t)src_sched->n_hub_items * heads * 4))
     return fail(PPGAT_ERR_INVALID, "xgat_bwd_dz: workspace too small");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const ppgat::ItemsArg it{src_sched->item_row, src_sched->item_beg, src_sched->item_end, src_sched->n_items,
-                           src_sched->n_hub_items, src_sched->n_long_items};
   Timed t(PPGAT_K_BWD_EPI, st);
-  hipError_t e = ppgat::xgat_bwd_dz(it, row, csc_eid, dz_slot, heads, s_src, nstate, negative_slope, dropout_p, seed,
-                                    seed_used, dz, S, lds, static_cast<float*>(workspace), src_sched->hub_row,
-                                    src_sched->hub_ptr, src_sched->n_hubs, st);
+  hipError_t e = ppgat::xgat_bwd_dz(*src_sched, row, csc_eid, dz_slot, heads, s_src, nstate, negative_slope, dropout_p,
+                                    seed, seed_used, dz, S, lds, static_cast<float*>(workspace), st);
   if (e != hipSuccess) return hip_fail(e, "xgat_bwd_dz");
   return PPGAT_OK;
 }

@@ -10,14 +10,11 @@
 #include <stdint.h>
 
 #include "ppgat_internal.h"
+#include "ppgat_device.h"
 
 namespace ppgat {
 namespace {
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ float dot4(float4 a, float4 b) {
-  return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x)));
-}
 __device__ __forceinline__ int64_t clampi(int64_t v, int64_t n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
 __device__ __forceinline__ int64_t zrow(const int32_t* m, int64_t v) { return m ? m[v] : v; }
 

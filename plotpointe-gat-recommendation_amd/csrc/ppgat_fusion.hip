@@ -30,6 +30,7 @@
 
 #include "ppgat_internal.h"
 #include "ppgat_lanes.h"
+#include "ppgat_device.h"
 #include "ppgat_split.h"
 #include "ppgat_nnh_pipe.h"
 
@@ -45,9 +46,6 @@ constexpr int kW1Floats = H1 * LW1;
 constexpr int kG2Floats = 4 * 32 * LH + DO * LH;
 constexpr int kLdsFloats = kW1Floats > kG2Floats ? kW1Floats : kG2Floats;
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float comp(const float4& v, int e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
 __device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
 }

@@ -44,46 +44,20 @@
 
 #pragma clang fp contract(off)
 
+#include "ppgat_device.h"  // after the pragma: its mul4 / add4 must not contract to FMAs here either
+
 namespace ppgat {
 namespace {
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float4 f4(float a) { return make_float4(a, a, a, a); }
-__device__ __forceinline__ float4 fma4(float s, float4 v, float4 a) {
-  return make_float4(fmaf(s, v.x, a.x), fmaf(s, v.y, a.y), fmaf(s, v.z, a.z), fmaf(s, v.w, a.w));
-}
-__device__ __forceinline__ float4 add4(float4 a, float4 b) {
-  return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
-}
-__device__ __forceinline__ float4 mul4(float4 a, float s) { return make_float4(a.x * s, a.y * s, a.z * s, a.w * s); }
-__device__ __forceinline__ float dot4(float4 a, float4 b) {
-  return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x)));
-}
-__device__ __forceinline__ float4 shfl_xor4(float4 v, int m) {
-  return make_float4(__shfl_xor(v.x, m), __shfl_xor(v.y, m), __shfl_xor(v.z, m), __shfl_xor(v.w, m));
-}
-// torch leaky_relu and its backward rule (slope where t <= 0)
-__device__ __forceinline__ float leaky(float t, float slope) { return t > 0.f ? t : t * slope; }
+// lrelu per component
 __device__ __forceinline__ float4 leaky4(float4 t, float slope) {
-  return make_float4(leaky(t.x, slope), leaky(t.y, slope), leaky(t.z, slope), leaky(t.w, slope));
+  return make_float4(lrelu(t.x, slope), lrelu(t.y, slope), lrelu(t.z, slope), lrelu(t.w, slope));
 }
 // de * att (.) leaky'(t)
 __device__ __forceinline__ float4 dleaky4(float de, float4 att, float4 t, float slope) {
   const float4 c = mul4(att, de);
   return make_float4(t.x > 0.f ? c.x : c.x * slope, t.y > 0.f ? c.y : c.y * slope, t.z > 0.f ? c.z : c.z * slope,
                      t.w > 0.f ? c.w : c.w * slope);
-}
-
-// the counter-hash dropout multiplier of ppgat_kernels.hip drop_scale (oracle/gat_oracle.py
-// dropout_scale restates it); the seed is the forward's effective seed (seed_used)
-__device__ __forceinline__ float drop_scale(uint64_t seed, uint32_t eid, uint32_t head, float p, float inv_keep) {
-  uint64_t x = seed ^ ((uint64_t)eid * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)head * 0xC2B2AE3D27D4EB4Full);
-  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27; x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  const float u = (float)(x >> 40) * (1.0f / 16777216.0f);
-  return u >= p ? inv_keep : 0.f;
 }
 
 template <int H, int C>
@@ -94,14 +68,6 @@ struct Geo {
   static constexpr int W = H * C;       // floats per node row
   static_assert(C == 32 || C == 64 || C == 128, "gatv2: C in {32, 64, 128}");
   static_assert(H == 1 || H == 2 || H == 4, "gatv2: H in {1, 2, 4}");
-};
-
-struct Items {
-  const int32_t* row;
-  const int32_t* beg;
-  const int32_t* end;
-  int64_t n_items;
-  int64_t n_hub_items;  // items [0, n_hub_items) are hub pieces, slot = item index
 };
 
 // online-softmax merge of (mo, lo, ao) into (m, l, a); -inf marks a state without edges
@@ -490,20 +456,20 @@ inline Offsets carve(int64_t n, int64_t src_hub_items, int64_t dst_hub_items, in
 }
 
 template <int H, int C>
-hipError_t fwd_t(const ItemsArg& it, const int32_t* col, const int32_t* eid, const FwdArgs& a,
-                 const int32_t* hub_row, const int32_t* hub_ptr, int64_t n_hubs, hipStream_t st) {
-  const Items its{it.row, it.beg, it.end, it.n_items, it.n_hub_items};
-  hipLaunchKernelGGL((k_v2_fwd<H, C>), dim3((unsigned)((it.n_items + 3) / 4)), dim3(256), 0, st, its, col, eid, a);
-  if (n_hubs > 0)
-    hipLaunchKernelGGL((k_v2_fwd_merge<H, C>), dim3((unsigned)((n_hubs + 3) / 4)), dim3(256), 0, st, hub_row,
-                       hub_ptr, n_hubs, a);
+hipError_t fwd_t(const ppgat_schedule& sch, const int32_t* col, const int32_t* eid, const FwdArgs& a,
+                 hipStream_t st) {
+  const Items its = items_of(sch, sch.n_items);
+  hipLaunchKernelGGL((k_v2_fwd<H, C>), dim3((unsigned)((sch.n_items + 3) / 4)), dim3(256), 0, st, its, col, eid,
+                     a);
+  if (sch.n_hubs > 0)
+    hipLaunchKernelGGL((k_v2_fwd_merge<H, C>), dim3((unsigned)((sch.n_hubs + 3) / 4)), dim3(256), 0, st,
+                       sch.hub_row, sch.hub_ptr, sch.n_hubs, a);
   return hipGetLastError();
 }
 
 template <int H, int C>
-hipError_t bwd_t(const ItemsArg& src, const int32_t* src_hub_row, const int32_t* src_hub_ptr, int64_t src_hubs,
-                 const ItemsArg& dst, const int32_t* dst_hub_row, const int32_t* dst_hub_ptr, int64_t dst_hubs,
-                 const int32_t* row, const int32_t* csc_eid, const int32_t* col, const int32_t* csr_eid, int64_t n,
+hipError_t bwd_t(const ppgat_schedule& src, const ppgat_schedule& dst, const int32_t* row, const int32_t* csc_eid,
+                 const int32_t* col, const int32_t* csr_eid, int64_t n,
                  BwdArgs a, float* dxl, float* dxr, float* datt, float* dbias, char* ws, hipStream_t st) {
   const Offsets o = carve(n, src.n_hub_items, dst.n_hub_items, H, C);
   float* bias_part = reinterpret_cast<float*>(ws + o.bias_part);
@@ -518,24 +484,24 @@ hipError_t bwd_t(const ItemsArg& src, const int32_t* src_hub_row, const int32_t*
     if (e != hipSuccess) return e;
   }
   constexpr int W4 = H * C / 4;
-  const Items si{src.row, src.beg, src.end, src.n_items, src.n_hub_items};
-  const Items di{dst.row, dst.beg, dst.end, dst.n_items, dst.n_hub_items};
+  const Items si = items_of(src, src.n_items);
+  const Items di = items_of(dst, dst.n_items);
   const unsigned dgrid = bwd_grid(dst.n_items);
   a.dx = nullptr;
   hipLaunchKernelGGL((k_v2_bwd<H, C, kDsum>), dim3(dgrid), dim3(256), 0, st, di, col, csr_eid, a);
-  if (dst_hubs > 0)
-    hipLaunchKernelGGL(k_v2_d_merge, dim3((unsigned)((dst_hubs * H + 255) / 256)), dim3(256), 0, st, dst_hub_row,
-                       dst_hub_ptr, dst_hubs, H, a.d_part, a.m, a.invl, a.nstate);
+  if (dst.n_hubs > 0)
+    hipLaunchKernelGGL(k_v2_d_merge, dim3((unsigned)((dst.n_hubs * H + 255) / 256)), dim3(256), 0, st,
+                       dst.hub_row, dst.hub_ptr, dst.n_hubs, H, a.d_part, a.m, a.invl, a.nstate);
   a.dx = dxl;
   hipLaunchKernelGGL((k_v2_bwd<H, C, kSrc>), dim3(bwd_grid(src.n_items)), dim3(256), 0, st, si, row, csc_eid, a);
-  if (src_hubs > 0)
-    hipLaunchKernelGGL(k_v2_row_merge, dim3((unsigned)((src_hubs * W4 + 255) / 256)), dim3(256), 0, st, src_hub_row,
-                       src_hub_ptr, src_hubs, W4, a.partial, dxl);
+  if (src.n_hubs > 0)
+    hipLaunchKernelGGL(k_v2_row_merge, dim3((unsigned)((src.n_hubs * W4 + 255) / 256)), dim3(256), 0, st,
+                       src.hub_row, src.hub_ptr, src.n_hubs, W4, a.partial, dxl);
   a.dx = dxr;
   hipLaunchKernelGGL((k_v2_bwd<H, C, kDst>), dim3(dgrid), dim3(256), 0, st, di, col, csr_eid, a);
-  if (dst_hubs > 0)
-    hipLaunchKernelGGL(k_v2_row_merge, dim3((unsigned)((dst_hubs * W4 + 255) / 256)), dim3(256), 0, st, dst_hub_row,
-                       dst_hub_ptr, dst_hubs, W4, a.partial, dxr);
+  if (dst.n_hubs > 0)
+    hipLaunchKernelGGL(k_v2_row_merge, dim3((unsigned)((dst.n_hubs * W4 + 255) / 256)), dim3(256), 0, st,
+                       dst.hub_row, dst.hub_ptr, dst.n_hubs, W4, a.partial, dxr);
   hipError_t e = launch_col_reduce(a.att_part, dgrid, H * C, H * C, datt, nullptr, st);
   if (e != hipSuccess) return e;
   return hipGetLastError();
@@ -567,25 +533,22 @@ size_t gatv2_bwd_workspace_bytes(int64_t n, int64_t src_hub_items, int64_t dst_h
   return carve(n, src_hub_items, dst_hub_items, H, C).total;
 }
 
-hipError_t gatv2_fwd(const ItemsArg& it, const int32_t* col, const int32_t* eid, int H, int C, const float* xl,
-                     const float* xr, const float* att, const float* bias, float slope, float p,
-                     const uint64_t* seed, float* out, float* m, float* invl, float* partial,
-                     const int32_t* hub_row, const int32_t* hub_ptr, int64_t n_hubs, hipStream_t st) {
-  if (it.n_items <= 0) return hipSuccess;
+hipError_t gatv2_fwd(const ppgat_schedule& sch, const int32_t* col, const int32_t* eid, int H, int C,
+                     const float* xl, const float* xr, const float* att, const float* bias, float slope, float p,
+                     const uint64_t* seed, float* out, float* m, float* invl, float* partial, hipStream_t st) {
+  if (sch.n_items <= 0) return hipSuccess;
   const FwdArgs a{xl, xr, att, bias, slope, p, p > 0.f ? 1.f / (1.f - p) : 1.f, seed, out, m, invl, partial};
-  PPGAT_V2_DISPATCH(H, C, (fwd_t<HH, CC>(it, col, eid, a, hub_row, hub_ptr, n_hubs, st)));
+  PPGAT_V2_DISPATCH(H, C, (fwd_t<HH, CC>(sch, col, eid, a, st)));
 }
 
-hipError_t gatv2_bwd(const ItemsArg& src, const int32_t* src_hub_row, const int32_t* src_hub_ptr, int64_t src_hubs,
-                     const ItemsArg& dst, const int32_t* dst_hub_row, const int32_t* dst_hub_ptr, int64_t dst_hubs,
-                     const int32_t* row, const int32_t* csc_eid, const int32_t* col, const int32_t* csr_eid,
+hipError_t gatv2_bwd(const ppgat_schedule& src, const ppgat_schedule& dst, const int32_t* row, const int32_t* csc_eid,
+                     const int32_t* col, const int32_t* csr_eid,
                      int64_t n, int H, int C, const float* xl, const float* xr, const float* att, const float* m,
                      const float* invl, const float* g, float slope, float p, const uint64_t* seed, float* dxl,
                      float* dxr, float* datt, float* dbias, void* ws, hipStream_t st) {
   BwdArgs a{xl,  xr,      att,     g,       m,       invl,    nullptr, slope, p, p > 0.f ? 1.f / (1.f - p) : 1.f,
             seed, nullptr, nullptr, nullptr, nullptr};
-  PPGAT_V2_DISPATCH(H, C, (bwd_t<HH, CC>(src, src_hub_row, src_hub_ptr, src_hubs, dst, dst_hub_row, dst_hub_ptr,
-                                        dst_hubs, row, csc_eid, col, csr_eid, n, a, dxl, dxr, datt, dbias,
+  PPGAT_V2_DISPATCH(H, C, (bwd_t<HH, CC>(src, dst, row, csc_eid, col, csr_eid, n, a, dxl, dxr, datt, dbias,
                                         static_cast<char*>(ws), st)));
 }
 

@@ -34,6 +34,7 @@
 
 #include "ppgat_internal.h"
 #include "ppgat_lanes.h"
+#include "ppgat_device.h"
 #include "ppgat_split.h"
 
 // Projection kernel occupancy: 2 waves per SIMD (256 VGPRs, two workgroups per CU).
@@ -48,9 +49,6 @@ namespace {
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 using u32x4 = __attribute__((__vector_size__(4 * sizeof(unsigned int)))) unsigned int;
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float comp(const float4& v, int e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
 __device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
 }
@@ -70,6 +68,7 @@ using gfloat = __attribute__((address_space(1))) const float;
 __device__ __forceinline__ gfloat* sgpr(const float* p) {
   return (gfloat*)(uintptr_t)sgpr((int64_t)reinterpret_cast<uintptr_t>(p));
 }
+using ppgat::ld4;  // the overload below would otherwise hide the shared one
 __device__ __forceinline__ float4 ld4(gfloat* p) {
   using v4 = __attribute__((ext_vector_type(4))) float;
   const v4 v = *(__attribute__((address_space(1))) const v4*)p;

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stddef.h>
 
+#include "../../include/ppgat.h"
+
 namespace ppgat {
 
 constexpr int kModePyg = 0;
@@ -15,36 +17,23 @@ constexpr int kMaxHeads = 8;
 constexpr int64_t kEpiMaxBlocks = PPGAT_EPI_BLOCKS;
 constexpr int kShortItemEdges = 16;  // include/ppgat.h PPGAT_SHORT_ITEM_EDGES
 
-// host-side view of a work schedule (see include/ppgat.h ppgat_schedule)
-struct ItemsArg {
-  const int32_t* row;
-  const int32_t* beg;
-  const int32_t* end;
-  int64_t n_items;
-  int64_t n_hub_items;
-  int64_t n_long_items;  // -1: unknown (no four-per-wave short-item path)
-};
-
 hipError_t launch_stream_copy(const void* src, void* dst, int64_t n_bytes, hipStream_t st);
 hipError_t launch_scores(const float* h, const float* as, const float* ad, int64_t n, int heads, int C, float* ss,
                          float* sd, hipStream_t st);
-hipError_t launch_fwd(const ItemsArg& it, const int32_t* col, const int32_t* eid, int heads, int C,
+hipError_t launch_fwd(const ppgat_schedule& sch, const int32_t* col, const int32_t* eid, int heads, int C,
                       const float* h, const float* ss, const float* sd, const float* bias, int mode, float slope,
                       float eps, float p, uint64_t seed, uint64_t* seed_out, float* out, float* m, float* invl,
-                      float* agg, float* partial, const int32_t* hub_row, const int32_t* hub_ptr, int64_t n_hubs,
-                      hipStream_t st);
+                      float* agg, float* partial, hipStream_t st);
 hipError_t launch_bwd_pro(const float* go, const float* out, const float* agg, const float* bias, const float* sd,
                           const float* m, const float* invl, int64_t n, int heads, int C, float gscale,
                           float* nstate, float* bias_part, int64_t blocks, hipStream_t st);
-hipError_t launch_bwd_src(const ItemsArg& it, const int32_t* row, const int32_t* csc_eid, const int32_t* csc2csr,
+hipError_t launch_bwd_src(const ppgat_schedule& sch, const int32_t* row, const int32_t* csc_eid, const int32_t* csc2csr,
                           int heads, int C, const float* h, const float* ss, const float* nstate, const float* go,
                           int mode, float slope, float gscale, float p, uint64_t seed, const uint64_t* seed_in,
-                          float* dh, int64_t ld_dh,
-                          float* ds_src, int64_t ld_ds, float* dz, float* partial, const int32_t* hub_row,
-                          const int32_t* hub_ptr, int64_t n_hubs, hipStream_t st);
-hipError_t launch_dst_sum(const ItemsArg& it, int heads, const float* dz, const int32_t* csr2csc, float* ds_dst,
-                          int64_t ld, float* partial, const int32_t* hub_row, const int32_t* hub_ptr, int64_t n_hubs,
+                          float* dh, int64_t ld_dh, float* ds_src, int64_t ld_ds, float* dz, float* partial,
                           hipStream_t st);
+hipError_t launch_dst_sum(const ppgat_schedule& sch, int heads, const float* dz, const int32_t* csr2csc, float* ds_dst,
+                          int64_t ld, float* partial, hipStream_t st);
 hipError_t launch_invert_index(const int32_t* p, int64_t n, int32_t* inv, hipStream_t st);
 int64_t epi_blocks(int64_t n);
 hipError_t launch_bwd_epi(const int32_t* rowptr, int64_t n, int heads, int C, const float* h, const float* as,
@@ -161,23 +150,20 @@ hipError_t bpr_sample_positives(const int64_t* ptr, const int32_t* items_orig, c
 // LightGCN propagation hop (ppgat_lgcn.hip); src1 / acc1 == NULL: one segment
 bool lgcn_channels_ok(int C);
 size_t lgcn_workspace_bytes(int64_t n_hub_items, int C);
-hipError_t lgcn_hop(const ItemsArg& it, const int32_t* col, const float* val, int C, const float* src0,
+hipError_t lgcn_hop(const ppgat_schedule& sch, const int32_t* col, const float* val, int C, const float* src0,
                     const float* src1, int64_t src_split, const float* acc0, const float* acc1, int64_t acc_split,
-                    float div, float* out, float* accw, float* partial, const int32_t* hub_row,
-                    const int32_t* hub_ptr, int64_t n_hubs, hipStream_t st);
+                    float div, float* out, float* accw, float* partial, hipStream_t st);
 
 // GATv2 dynamic-attention layer (ppgat_gatv2.hip); seed: the device slot holding the effective
 // mask seed (read when p > 0)
 bool gatv2_shape_ok(int H, int C);
 size_t gatv2_fwd_workspace_bytes(int64_t n_hub_items, int H, int C);
 size_t gatv2_bwd_workspace_bytes(int64_t n, int64_t src_hub_items, int64_t dst_hub_items, int H, int C);
-hipError_t gatv2_fwd(const ItemsArg& it, const int32_t* col, const int32_t* eid, int H, int C, const float* xl,
-                     const float* xr, const float* att, const float* bias, float slope, float p,
-                     const uint64_t* seed, float* out, float* m, float* invl, float* partial,
-                     const int32_t* hub_row, const int32_t* hub_ptr, int64_t n_hubs, hipStream_t st);
-hipError_t gatv2_bwd(const ItemsArg& src, const int32_t* src_hub_row, const int32_t* src_hub_ptr, int64_t src_hubs,
-                     const ItemsArg& dst, const int32_t* dst_hub_row, const int32_t* dst_hub_ptr, int64_t dst_hubs,
-                     const int32_t* row, const int32_t* csc_eid, const int32_t* col, const int32_t* csr_eid,
+hipError_t gatv2_fwd(const ppgat_schedule& sch, const int32_t* col, const int32_t* eid, int H, int C,
+                     const float* xl, const float* xr, const float* att, const float* bias, float slope, float p,
+                     const uint64_t* seed, float* out, float* m, float* invl, float* partial, hipStream_t st);
+hipError_t gatv2_bwd(const ppgat_schedule& src, const ppgat_schedule& dst, const int32_t* row, const int32_t* csc_eid,
+                     const int32_t* col, const int32_t* csr_eid,
                      int64_t n, int H, int C, const float* xl, const float* xr, const float* att, const float* m,
                      const float* invl, const float* g, float slope, float p, const uint64_t* seed, float* dxl,
                      float* dxr, float* datt, float* dbias, void* ws, hipStream_t st);
@@ -232,7 +218,8 @@ hipError_t infonce(const float* F, const float* T, const float* I, int64_t B, fl
                    float* dT, float* dI, void* ws, hipStream_t st);
 hipError_t relu_dropout(const float* z, int64_t n, float p, uint64_t seed, int backward, float* a, hipStream_t st);
 
-// aggregate-then-transform multi-head layer and fp32 MFMA GEMMs (ppgat_xform.hip)
+// matrix-core GEMMs (ppgat_xform.hip) and the aggregate-then-transform multi-head layer
+// (ppgat_xgat.hip: att_proj, rank_update, xgat_*, colsum)
 hipError_t seed_snapshot(uint64_t seed, uint64_t* out, hipStream_t st);
 bool gemm_nn_shape_ok(int64_t M, int K, int N, int bmode);
 // split-bf16 matrix-core GEMMs on (default) or the fp32 MFMA kernels (PPGAT_GEMM=fp32)
@@ -265,32 +252,31 @@ hipError_t xgat_weights(const float* W, const float* att_src, const float* att_d
                         float* Wt, float* Wg, hipStream_t st);
 hipError_t xgat_scores(const float* x, int64_t ldx, int64_t n_rows, int64_t n_dst, int K, int H, const float* A,
                        float* s_src, float* s_dst, hipStream_t st);
-hipError_t xgat_fwd(const ItemsArg& it, const int32_t* col, const int32_t* eid, const float* x, int64_t ldx, int K,
-                    int H, const float* s_src, const float* s_dst, float slope, float p, uint64_t seed,
-                    const uint64_t* seed_in, float* agg, float* m, float* invl, float* partial,
-                    const int32_t* hub_row, const int32_t* hub_ptr, int64_t n_hubs, hipStream_t st,
+hipError_t xgat_fwd(const ppgat_schedule& sch, const int32_t* col, const int32_t* eid, const float* x, int64_t ldx,
+                    int K, int H, const float* s_src, const float* s_dst, float slope, float p, uint64_t seed,
+                    const uint64_t* seed_in, float* agg, float* m, float* invl, float* partial, hipStream_t st,
                     unsigned* xmax = nullptr);
 hipError_t xgat_bwd_pro(const float* gt, const float* agg, const float* s_dst, const float* m, const float* invl,
                         int64_t n, int K, int H, float* nstate, hipStream_t st);
-hipError_t xgat_bwd_edges(const ItemsArg& it, const int32_t* row, const int32_t* csc_eid, const int32_t* csc2csr,
+hipError_t xgat_bwd_edges(const ppgat_schedule& sch, const int32_t* row, const int32_t* csc_eid,
+                          const int32_t* csc2csr,
                           const float* x, int64_t ldx, int K, int H, const float* s_src, const float* nstate,
                           const float* gt, const float* A_src, float slope, float p, uint64_t seed,
                           const uint64_t* seed_in, float* dx, int64_t lddx, float* S, int64_t lds, float* dz,
-                          float* partial, const int32_t* hub_row, const int32_t* hub_ptr, int64_t n_hubs,
-                          hipStream_t st);
-hipError_t xgat_bwd_edges_g(const ItemsArg& it, const int32_t* row, const int32_t* csc_eid, const int32_t* csc2csr,
+                          float* partial, hipStream_t st);
+hipError_t xgat_bwd_edges_g(const ppgat_schedule& sch, const int32_t* row, const int32_t* csc_eid,
+                            const int32_t* csc2csr,
                             const float* hs, int C, int H, const float* s_src, const float* nstate, const float* g,
                             int64_t ldg, float slope, float p, uint64_t seed, const uint64_t* seed_in, float* acc,
-                            float* S, int64_t lds, float* dz, float* partial, const int32_t* hub_row,
-                            const int32_t* hub_ptr, int64_t n_hubs, hipStream_t st, float* pz = nullptr,
+                            float* S, int64_t lds, float* dz, float* partial, hipStream_t st, float* pz = nullptr,
                             unsigned* gmax = nullptr);
 hipError_t xgat_nstate_set_d(float* nstate, const float* D, int64_t n, int H, hipStream_t st);
 hipError_t xgat_nstate(const float* s_dst, const float* m, const float* invl, const float* D, int64_t n, int H,
                        float* nstate, hipStream_t st);
-hipError_t xgat_bwd_dz(const ItemsArg& it, const int32_t* row, const int32_t* csc_eid, const int32_t* csc2csr, int H,
+hipError_t xgat_bwd_dz(const ppgat_schedule& sch, const int32_t* row, const int32_t* csc_eid, const int32_t* csc2csr,
+                       int H,
                        const float* s_src, const float* nstate, float slope, float p, uint64_t seed,
-                       const uint64_t* seed_in, float* dz, float* S, int64_t lds, float* partial,
-                       const int32_t* hub_row, const int32_t* hub_ptr, int64_t n_hubs, hipStream_t st);
+                       const uint64_t* seed_in, float* dz, float* S, int64_t lds, float* partial, hipStream_t st);
 hipError_t xgat_bwd_epi(const float* S, int64_t lds, const float* A_dst, int64_t n, int K, int H, float* dx,
                         int64_t lddx, hipStream_t st);
 hipError_t xgat_wgrad(const float* G, const float* GV, const float* W, const float* att_src, const float* att_dst,

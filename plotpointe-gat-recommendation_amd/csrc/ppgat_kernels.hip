@@ -28,6 +28,7 @@
 
 #include "ppgat_internal.h"
 #include "ppgat_lanes.h"
+#include "ppgat_device.h"
 
 #ifndef PPGAT_PRO_UP
 #define PPGAT_PRO_UP 4
@@ -38,32 +39,16 @@
 
 namespace ppgat {
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float4 f4(float a) { return make_float4(a, a, a, a); }
-__device__ __forceinline__ float4 fma4(float s, float4 v, float4 a) {
-  return make_float4(fmaf(s, v.x, a.x), fmaf(s, v.y, a.y), fmaf(s, v.z, a.z), fmaf(s, v.w, a.w));
-}
-__device__ __forceinline__ float4 add4(float4 a, float4 b) {
-  return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
-}
-__device__ __forceinline__ float4 mul4(float4 a, float s) { return make_float4(a.x * s, a.y * s, a.z * s, a.w * s); }
-__device__ __forceinline__ float dot4(float4 a, float4 b) {
-  return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x)));
-}
-__device__ __forceinline__ float4 shfl_xor4(float4 v, int m) {
-  return make_float4(__shfl_xor(v.x, m), __shfl_xor(v.y, m), __shfl_xor(v.z, m), __shfl_xor(v.w, m));
-}
 // attention logit e(z) and de/dz, per mode (torch leaky_relu / clamp backward rules:
 // slope where z <= 0; clamp passes gradient where min <= e <= max).
 __device__ __forceinline__ float logit(float z, float slope, int mode) {
-  float e = z > 0.f ? z : z * slope;
+  float e = lrelu(z, slope);
   if (mode == kModeCustom) e = fminf(fmaxf(e, -10.f), 10.f);
   return e;
 }
 __device__ __forceinline__ float dlogit(float z, float slope, int mode) {
-  const float e = z > 0.f ? z : z * slope;
-  float d = z > 0.f ? 1.f : slope;
+  const float e = lrelu(z, slope);
+  float d = dlrelu(z, slope);
   if (mode == kModeCustom && (e < -10.f || e > 10.f)) d = 0.f;
   return d;
 }
@@ -86,40 +71,8 @@ __global__ void k_seed_snap(uint64_t seed, uint64_t* __restrict__ out) {
   if (threadIdx.x == 0) out[0] = epoch_seed(seed);
 }
 
-// Counter-based dropout mask on alpha (restated in oracle/gat_oracle.py:dropout_scale).
-__device__ __forceinline__ float drop_scale(uint64_t seed, uint32_t eid, uint32_t head, float p,
-                                            float inv_keep) {
-  uint64_t x = seed ^ ((uint64_t)eid * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)head * 0xC2B2AE3D27D4EB4Full);
-  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27; x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  const float u = (float)(x >> 40) * (1.0f / 16777216.0f);
-  return u >= p ? inv_keep : 0.f;
-}
-
-// Streamed (once-touched) rows of the edge kernels -- the forward's output rows, pass B's own
-// source rows h_j and dh_j -- with the non-temporal hint when PPGAT_NT_STREAM=1, so they do
-// not push the gathered table (h forward, grad_out in pass B) out of the Infinity Cache.
-#ifndef PPGAT_NT_STREAM
-#define PPGAT_NT_STREAM 1
-#endif
-__device__ __forceinline__ float4 ld4s(const float* p) {
-#if PPGAT_NT_STREAM
-  using v4 = __attribute__((ext_vector_type(4))) float;
-  const v4 v = __builtin_nontemporal_load(reinterpret_cast<const v4*>(p));
-  return make_float4(v.x, v.y, v.z, v.w);
-#else
-  return *reinterpret_cast<const float4*>(p);
-#endif
-}
-__device__ __forceinline__ void st4s(float* p, float4 a) {
-#if PPGAT_NT_STREAM
-  using v4 = __attribute__((ext_vector_type(4))) float;
-  __builtin_nontemporal_store(v4{a.x, a.y, a.z, a.w}, reinterpret_cast<v4*>(p));
-#else
-  *reinterpret_cast<float4*>(p) = a;
-#endif
-}
+// The streamed rows (ld4s / st4s) here are the forward's output rows and pass B's own source
+// rows h_j and dh_j; the gathered table they spare is h forward, grad_out in pass B.
 
 template <int C>
 struct Geo {
@@ -153,22 +106,6 @@ __global__ void __launch_bounds__(256) k_scores(const float* __restrict__ h, con
     s_dst[pr] = y;
   }
 }
-
-// ---------------------------------------------------------------------------
-// Work items.  Rows (dst rows for the forward, src rows for backward pass B) are
-// cut into items of at most T edges by ppgat_schedule_build: hub rows (deg > T) become
-// ceil(deg/T) pieces that write partial state to a scratch slab and are merged in
-// piece order by a second small kernel (deterministic); all other rows are one item.
-// Items are ordered hub pieces first, then rows by descending degree, so the longest
-// work starts first and the tail is short (largest in-degree on config 2: 5,180).
-// ---------------------------------------------------------------------------
-struct Items {
-  const int32_t* row;
-  const int32_t* beg;
-  const int32_t* end;
-  int64_t n_items;
-  int64_t n_hub_items;  // items [0, n_hub_items) are hub pieces, slot = item index
-};
 
 // ---------------------------------------------------------------------------
 // Fused forward: one wave per item (destination row or hub piece), CSR by dst.
@@ -1166,10 +1103,10 @@ hipError_t launch_scores(const float* h, const float* as, const float* ad, int64
 
 // First item of the four-per-wave short path, or n_items when every item takes the
 // one-per-wave kernel (heads > 1, C < 64, or a schedule without n_long_items).
-static int64_t short_begin(const ItemsArg& it, int heads, int C) {
-  if (heads != 1 || (C != 64 && C != 128 && C != 256)) return it.n_items;
-  if (it.n_long_items < it.n_hub_items || it.n_long_items > it.n_items) return it.n_items;
-  return it.n_long_items;
+static int64_t short_begin(const ppgat_schedule& sch, int heads, int C) {
+  if (heads != 1 || (C != 64 && C != 128 && C != 256)) return sch.n_items;
+  if (sch.n_long_items < sch.n_hub_items || sch.n_long_items > sch.n_items) return sch.n_items;
+  return sch.n_long_items;
 }
 
 #define PPGAT_DISPATCH_C64(C, ...)                             \
@@ -1179,36 +1116,35 @@ static int64_t short_begin(const ItemsArg& it, int heads, int C) {
     else { constexpr int CC = 256; __VA_ARGS__; }              \
   } while (0)
 
-hipError_t launch_fwd(const ItemsArg& it, const int32_t* col, const int32_t* eid, int heads, int C,
+hipError_t launch_fwd(const ppgat_schedule& sch, const int32_t* col, const int32_t* eid, int heads, int C,
                       const float* h, const float* ss, const float* sd, const float* bias, int mode, float slope,
                       float eps, float p, uint64_t seed, uint64_t* seed_out, float* out, float* m, float* invl,
-                      float* agg, float* partial, const int32_t* hub_row, const int32_t* hub_ptr, int64_t n_hubs,
-                      hipStream_t st) {
+                      float* agg, float* partial, hipStream_t st) {
   const float inv_keep = p > 0.f ? 1.f / (1.f - p) : 1.f;
   // the effective mask seed is written by block 0 of the first edge kernel launched (no
   // separate launch); a graph without items snapshots it with k_seed_snap
-  const int64_t n_long = short_begin(it, heads, C);
-  const Items its{it.row, it.beg, it.end, n_long, it.n_hub_items};
-  if (seed_out != nullptr && it.n_items == 0) hipLaunchKernelGGL(k_seed_snap, dim3(1), dim3(64), 0, st, seed, seed_out);
+  const int64_t n_long = short_begin(sch, heads, C);
+  const Items its = items_of(sch, n_long);
+  if (seed_out != nullptr && sch.n_items == 0) hipLaunchKernelGGL(k_seed_snap, dim3(1), dim3(64), 0, st, seed, seed_out);
   if (n_long > 0) {
     PPGAT_DISPATCH_C(C, hipLaunchKernelGGL(k_fwd<CC>, dim3(blocks_for(n_long * 64)), dim3(256), 0, st, its, col,
                                            eid, heads, h, ss, sd, bias, mode, slope, eps, p, inv_keep, seed, out, m,
                                            invl, agg, partial, seed_out));
   }
   // the hub merges ride at the head of the short-item launch when there is one (one launch fewer)
-  const bool fold = n_long < it.n_items;
+  const bool fold = n_long < sch.n_items;
   if (fold) {
-    const Items all{it.row, it.beg, it.end, it.n_items, it.n_hub_items};
-    const HubMerge mg{hub_row, hub_ptr, n_hubs, heads, partial, n_hubs > 0 ? (n_hubs + 3) / 4 : 0};
-    const unsigned g = (unsigned)((it.n_items - n_long + 15) / 16 + mg.mblocks);  // 4 waves x 4 items per block
+    const Items all = items_of(sch, sch.n_items);
+    const HubMerge mg{sch.hub_row, sch.hub_ptr, sch.n_hubs, heads, partial, sch.n_hubs > 0 ? (sch.n_hubs + 3) / 4 : 0};
+    const unsigned g = (unsigned)((sch.n_items - n_long + 15) / 16 + mg.mblocks);  // 4 waves x 4 items per block
     PPGAT_DISPATCH_C64(C, hipLaunchKernelGGL(k_fwd_short<CC>, dim3(g), dim3(256), 0, st, all, n_long, col, eid, h,
                                              ss, sd, bias, mode, slope, eps, p, inv_keep, seed, out, m, invl, agg,
                                              n_long > 0 ? nullptr : seed_out, mg));
   }
-  if (n_hubs > 0 && !fold) {
-    PPGAT_DISPATCH_C(C, hipLaunchKernelGGL(k_fwd_merge<CC>, dim3(blocks_for(n_hubs * 64)), dim3(256), 0, st,
-                                           hub_row, hub_ptr, n_hubs, heads, partial, bias, mode, eps, out, m, invl,
-                                           agg));
+  if (sch.n_hubs > 0 && !fold) {
+    PPGAT_DISPATCH_C(C, hipLaunchKernelGGL(k_fwd_merge<CC>, dim3(blocks_for(sch.n_hubs * 64)), dim3(256), 0, st,
+                                           sch.hub_row, sch.hub_ptr, sch.n_hubs, heads, partial, bias, mode, eps, out,
+                                           m, invl, agg));
   }
   return hipGetLastError();
 }
@@ -1223,15 +1159,14 @@ hipError_t launch_bwd_pro(const float* go, const float* out, const float* agg, c
   return hipGetLastError();
 }
 
-hipError_t launch_bwd_src(const ItemsArg& it, const int32_t* row, const int32_t* csc_eid, const int32_t* csc2csr,
+hipError_t launch_bwd_src(const ppgat_schedule& sch, const int32_t* row, const int32_t* csc_eid, const int32_t* csc2csr,
                           int heads, int C, const float* h, const float* ss, const float* nstate, const float* go,
                           int mode, float slope, float gscale, float p, uint64_t seed, const uint64_t* seed_in,
-                          float* dh, int64_t ld_dh,
-                          float* ds_src, int64_t ld_ds, float* dz, float* partial, const int32_t* hub_row,
-                          const int32_t* hub_ptr, int64_t n_hubs, hipStream_t st) {
+                          float* dh, int64_t ld_dh, float* ds_src, int64_t ld_ds, float* dz, float* partial,
+                          hipStream_t st) {
   const float inv_keep = p > 0.f ? 1.f / (1.f - p) : 1.f;
-  const int64_t n_long = short_begin(it, heads, C);
-  const Items its{it.row, it.beg, it.end, n_long, it.n_hub_items};
+  const int64_t n_long = short_begin(sch, heads, C);
+  const Items its = items_of(sch, n_long);
   if (n_long > 0) {
     const bool mh = heads > 1 && C >= 32 && (heads == 2 || heads == 4 || heads == 8);
     if (mh) {  // every head of an edge in one pass (one grad_out gather per edge)
@@ -1251,19 +1186,20 @@ hipError_t launch_bwd_src(const ItemsArg& it, const int32_t* row, const int32_t*
     }
   }
   // the short items after the long ones, with the hub merges at the head of that launch
-  const bool fold = n_long < it.n_items;
+  const bool fold = n_long < sch.n_items;
   if (fold) {
-    const Items all{it.row, it.beg, it.end, it.n_items, it.n_hub_items};
-    const HubMerge mg{hub_row, hub_ptr, n_hubs, heads, partial, n_hubs > 0 ? (n_hubs + 3) / 4 : 0};
-    const unsigned g = (unsigned)((it.n_items - n_long + 15) / 16 + mg.mblocks);
+    const Items all = items_of(sch, sch.n_items);
+    const HubMerge mg{sch.hub_row, sch.hub_ptr, sch.n_hubs, heads, partial, sch.n_hubs > 0 ? (sch.n_hubs + 3) / 4 : 0};
+    const unsigned g = (unsigned)((sch.n_items - n_long + 15) / 16 + mg.mblocks);
     PPGAT_DISPATCH_C64(C, hipLaunchKernelGGL(k_bwd_src_short<CC>, dim3(g), dim3(256), 0, st, all, n_long, row,
                                              csc_eid, csc2csr, h, ss, reinterpret_cast<const float4*>(nstate), go,
                                              mode, slope, gscale, p, inv_keep, seed, seed_in, dh, ld_dh, ds_src, ld_ds,
                                              dz, mg));
   }
-  if (n_hubs > 0 && !fold) {
-    PPGAT_DISPATCH_C(C, hipLaunchKernelGGL(k_bwd_merge<CC>, dim3(blocks_for(n_hubs * 64)), dim3(256), 0, st,
-                                           hub_row, hub_ptr, n_hubs, heads, partial, dh, ld_dh, ds_src, ld_ds));
+  if (sch.n_hubs > 0 && !fold) {
+    PPGAT_DISPATCH_C(C, hipLaunchKernelGGL(k_bwd_merge<CC>, dim3(blocks_for(sch.n_hubs * 64)), dim3(256), 0, st,
+                                           sch.hub_row, sch.hub_ptr, sch.n_hubs, heads, partial, dh, ld_dh, ds_src,
+                                           ld_ds));
   }
   return hipGetLastError();
 }
@@ -1285,18 +1221,17 @@ hipError_t launch_bwd_epi(const int32_t* rowptr, int64_t n, int heads, int C, co
   return hipGetLastError();
 }
 
-hipError_t launch_dst_sum(const ItemsArg& it, int heads, const float* dz, const int32_t* csr2csc, float* ds_dst,
-                          int64_t ld, float* partial, const int32_t* hub_row, const int32_t* hub_ptr, int64_t n_hubs,
-                          hipStream_t st) {
-  const int64_t pairs = it.n_items * heads;
+hipError_t launch_dst_sum(const ppgat_schedule& sch, int heads, const float* dz, const int32_t* csr2csc, float* ds_dst,
+                          int64_t ld, float* partial, hipStream_t st) {
+  const int64_t pairs = sch.n_items * heads;
   if (pairs == 0) return hipSuccess;
-  const Items items{it.row, it.beg, it.end, it.n_items, it.n_hub_items};
+  const Items items = items_of(sch, sch.n_items);
   const bool aligned = (reinterpret_cast<uintptr_t>(dz) % (4 * heads)) == 0;
   if (csr2csc != nullptr && (heads == 2 || heads == 4) && aligned) {
     // the long items (and hub pieces) 16 lanes each; the short ones (known when the schedule
     // counted them) one thread each, the same bits (k_dst_sum_vh_short)
-    const int64_t nl = it.n_long_items >= 0 ? it.n_long_items : it.n_items;
-    const Items lng{it.row, it.beg, it.end, nl, it.n_hub_items};
+    const int64_t nl = sch.n_long_items >= 0 ? sch.n_long_items : sch.n_items;
+    const Items lng = items_of(sch, nl);
     if (nl > 0) {
       if (heads == 2)
         hipLaunchKernelGGL((k_dst_sum_vh<true, 2>), dim3(blocks_for(nl * 16)), dim3(256), 0, st, lng, dz, csr2csc,
@@ -1305,8 +1240,8 @@ hipError_t launch_dst_sum(const ItemsArg& it, int heads, const float* dz, const 
         hipLaunchKernelGGL((k_dst_sum_vh<true, 4>), dim3(blocks_for(nl * 16)), dim3(256), 0, st, lng, dz, csr2csc,
                            ds_dst, ld, partial);
     }
-    if (it.n_items > nl) {
-      const dim3 g(blocks_for(it.n_items - nl));
+    if (sch.n_items > nl) {
+      const dim3 g(blocks_for(sch.n_items - nl));
       if (heads == 2)
         hipLaunchKernelGGL((k_dst_sum_vh_short<2>), g, dim3(256), 0, st, items, nl, dz, csr2csc, ds_dst, ld);
       else
@@ -1318,9 +1253,9 @@ hipError_t launch_dst_sum(const ItemsArg& it, int heads, const float* dz, const 
   else
     hipLaunchKernelGGL(k_dst_sum<false>, dim3(blocks_for(pairs * 16)), dim3(256), 0, st, items, heads, dz, csr2csc,
                        ds_dst, ld, partial);
-  if (n_hubs > 0)
-    hipLaunchKernelGGL(k_dst_merge, dim3((unsigned)((n_hubs + 3) / 4)), dim3(256), 0, st, hub_row, hub_ptr, n_hubs,
-                       heads, partial, ds_dst, ld);
+  if (sch.n_hubs > 0)
+    hipLaunchKernelGGL(k_dst_merge, dim3((unsigned)((sch.n_hubs + 3) / 4)), dim3(256), 0, st, sch.hub_row, sch.hub_ptr,
+                       sch.n_hubs, heads, partial, ds_dst, ld);
   return hipGetLastError();
 }
 

@@ -25,33 +25,14 @@
 
 #include "ppgat_internal.h"
 #include "ppgat_lanes.h"
+#include "ppgat_device.h"
 
 namespace ppgat {
 namespace {
 
 constexpr int kSU = 4;  // neighbour rows in flight per short item (per 16-lane row)
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float4 f4(float a) { return make_float4(a, a, a, a); }
-__device__ __forceinline__ float4 fma4(float s, float4 v, float4 a) {
-  return make_float4(fmaf(s, v.x, a.x), fmaf(s, v.y, a.y), fmaf(s, v.z, a.z), fmaf(s, v.w, a.w));
-}
-__device__ __forceinline__ float4 add4(float4 a, float4 b) {
-  return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
-}
 __device__ __forceinline__ float4 div4(float4 a, float d) { return make_float4(a.x / d, a.y / d, a.z / d, a.w / d); }
-// once-touched rows (the running layer sum): non-temporal, so they do not push the gathered
-// table out of the Infinity Cache
-__device__ __forceinline__ float4 ld4s(const float* p) {
-  using v4 = __attribute__((ext_vector_type(4))) float;
-  const v4 v = __builtin_nontemporal_load(reinterpret_cast<const v4*>(p));
-  return make_float4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ void st4s(float* p, float4 a) {
-  using v4 = __attribute__((ext_vector_type(4))) float;
-  __builtin_nontemporal_store(v4{a.x, a.y, a.z, a.w}, reinterpret_cast<v4*>(p));
-}
 
 template <int C>
 struct Geo {
@@ -72,14 +53,6 @@ template <int C>
 __device__ __forceinline__ const float* row_of(const Rows& r, int j) {
   return j < r.split ? r.p0 + (int64_t)j * C : r.p1 + (int64_t)(j - r.split) * C;
 }
-
-struct Items {
-  const int32_t* row;
-  const int32_t* beg;
-  const int32_t* end;
-  int64_t n_items;
-  int64_t n_hub_items;  // items [0, n_hub_items) are hub pieces, slot = item index
-};
 
 // out / accw of one finished row.  accw may be acc_in's own buffer (in-place running sum):
 // each element is read and then written by the same lane.
@@ -236,22 +209,22 @@ inline Rows rows_arg(const float* p0, const float* p1, int64_t split) {
 }
 
 template <int C>
-hipError_t hop(const ItemsArg& it, const int32_t* col, const float* val, const Rows& src, const Epi& epi,
-               float* partial, const int32_t* hub_row, const int32_t* hub_ptr, int64_t n_hubs, hipStream_t st) {
+hipError_t hop(const ppgat_schedule& sch, const int32_t* col, const float* val, const Rows& src, const Epi& epi,
+               float* partial, hipStream_t st) {
   // first item of the four-per-wave path (n_items when the schedule does not know it)
-  int64_t n_long = it.n_long_items;
-  if (n_long < it.n_hub_items || n_long > it.n_items) n_long = it.n_items;
-  const Items its{it.row, it.beg, it.end, n_long, it.n_hub_items};
+  int64_t n_long = sch.n_long_items;
+  if (n_long < sch.n_hub_items || n_long > sch.n_items) n_long = sch.n_items;
+  const Items its = items_of(sch, n_long);
   if (n_long > 0)
     hipLaunchKernelGGL(k_lgcn_long<C>, dim3(blocks_for(n_long * 64)), dim3(256), 0, st, its, col, val, src, epi,
                        partial);
-  const bool fold = n_long < it.n_items;
-  HubMerge mg{hub_row, hub_ptr, n_hubs, partial, n_hubs > 0 ? (n_hubs + 3) / 4 : 0};
+  const bool fold = n_long < sch.n_items;
+  HubMerge mg{sch.hub_row, sch.hub_ptr, sch.n_hubs, partial, sch.n_hubs > 0 ? (sch.n_hubs + 3) / 4 : 0};
   if (fold) {
-    const Items all{it.row, it.beg, it.end, it.n_items, it.n_hub_items};
-    const unsigned g = (unsigned)((it.n_items - n_long + 15) / 16 + mg.mblocks);  // 4 waves x 4 items per block
+    const Items all = items_of(sch, sch.n_items);
+    const unsigned g = (unsigned)((sch.n_items - n_long + 15) / 16 + mg.mblocks);  // 4 waves x 4 items per block
     hipLaunchKernelGGL(k_lgcn_short<C>, dim3(g), dim3(256), 0, st, all, n_long, col, val, src, epi, mg);
-  } else if (n_hubs > 0) {
+  } else if (sch.n_hubs > 0) {
     hipLaunchKernelGGL(k_lgcn_merge<C>, dim3((unsigned)mg.mblocks), dim3(256), 0, st, mg, epi);
   }
   return hipGetLastError();
@@ -265,17 +238,16 @@ size_t lgcn_workspace_bytes(int64_t n_hub_items, int C) {
   return (((size_t)(n_hub_items > 0 ? n_hub_items : 1) * C * 4) + 255) & ~size_t(255);
 }
 
-hipError_t lgcn_hop(const ItemsArg& it, const int32_t* col, const float* val, int C, const float* src0,
+hipError_t lgcn_hop(const ppgat_schedule& sch, const int32_t* col, const float* val, int C, const float* src0,
                     const float* src1, int64_t src_split, const float* acc0, const float* acc1, int64_t acc_split,
-                    float div, float* out, float* accw, float* partial, const int32_t* hub_row,
-                    const int32_t* hub_ptr, int64_t n_hubs, hipStream_t st) {
-  if (it.n_items <= 0) return hipSuccess;
+                    float div, float* out, float* accw, float* partial, hipStream_t st) {
+  if (sch.n_items <= 0) return hipSuccess;
   const Rows src = rows_arg(src0, src1, src_split);
   const Epi epi{acc0 != nullptr ? rows_arg(acc0, acc1, acc_split) : Rows{nullptr, nullptr, 0}, div, out, accw};
   switch (C) {
-    case 64: return hop<64>(it, col, val, src, epi, partial, hub_row, hub_ptr, n_hubs, st);
-    case 128: return hop<128>(it, col, val, src, epi, partial, hub_row, hub_ptr, n_hubs, st);
-    case 256: return hop<256>(it, col, val, src, epi, partial, hub_row, hub_ptr, n_hubs, st);
+    case 64: return hop<64>(sch, col, val, src, epi, partial, st);
+    case 128: return hop<128>(sch, col, val, src, epi, partial, st);
+    case 256: return hop<256>(sch, col, val, src, epi, partial, st);
     default: return hipErrorInvalidValue;
   }
 }
