@@ -203,6 +203,46 @@ int ppgat_bwd_epilogue(const int32_t* rowptr, int64_t n_nodes, int heads, int ch
                        const float* att_src, const float* att_dst, const float* ds_src, const float* dz,
                        float* grad_h, float* grad_att_src, float* grad_att_dst, float* part, void* stream);
 
+/* ---- GATConv edge features (edge_dim = D) ----------------------------------
+ * Replaces: PyG GATConv(edge_dim=D): alpha_edge = (lin_edge(edge_attr).view(E, H, C) * att_edge).sum(-1)
+ *           added to the logit before leaky_relu.  The caller collapses the two parameters to
+ *           v [H, D], v[h, d] = sum_c att_edge[h, c] lin_edge.weight[h C + c, d]; then
+ *           alpha_edge[k, h] = <edge_attr[k, :], v[h, :]>.  D <= PPGAT_EDGE_MAX_DIM, heads <= 8.
+ * ppgat_edge_attr_permute: out[k, :] = edge_attr[slot_eid[k], :] -- edge_attr [E, D] brought into
+ *   the slot order of a view (slot_eid = csr_eid or csc_eid of ppgat_csr_build), once per graph
+ *   and attribute tensor.
+ * ppgat_edge_terms: t_csr[k, h] = <attr_csr[k, :], v[h, :]> and (t_csc != NULL) t_csc likewise
+ *   from attr_csc: the same fmaf chain over d for both, so an edge's term has the same bits in
+ *   either order.
+ * ppgat_edge_fwd / ppgat_edge_bwd_edges: ppgat_fwd / ppgat_bwd_edges with the logit
+ *   z = (s_src[j] + s_dst[i]) + edge_term[k, h] -- edge_term [E, H] in CSR slot order for the
+ *   forward, in CSC slot order for pass B.  Everything else as documented above.
+ * ppgat_edge_dv: dv[h, d] = sum_k dz[k, h] attr_csc[k, d] with dz [E, H] in CSC order (pass B
+ *   with dz_slot NULL).  A fixed grid leaves one partial row per block in part
+ *   [ppgat_edge_dv_partial_rows(E) * H * D], summed in block order: atomic-free, the same bits on
+ *   every launch.  E = 0 gives dv = 0.
+ */
+#define PPGAT_EDGE_MAX_DIM 16
+int ppgat_edge_attr_permute(const float* edge_attr, const int32_t* slot_eid, int64_t n_edges, int edge_dim,
+                            float* out, void* stream);
+int ppgat_edge_terms(const float* attr_csr, const float* attr_csc, const float* v, int64_t n_edges, int edge_dim,
+                     int heads, float* t_csr, float* t_csc, void* stream);
+int ppgat_edge_fwd(const ppgat_schedule* dst_sched, const int32_t* col, const int32_t* csr_eid,
+                   const float* edge_term, int64_t n_nodes, int64_t n_edges, int heads, int channels,
+                   const float* h, const float* s_src, const float* s_dst, const float* bias,
+                   int mode, float negative_slope, float dropout_p, uint64_t seed, uint64_t* seed_used,
+                   float* out, float* m, float* inv_l, float* agg,
+                   void* workspace, size_t workspace_bytes, void* stream);
+int ppgat_edge_bwd_edges(const ppgat_schedule* src_sched, const int32_t* row, const int32_t* csc_eid,
+                         const int32_t* dz_slot, const float* edge_term, int64_t n_edges, int heads, int channels,
+                         const float* h, const float* s_src, const float* nstate, const float* grad_out, int mode,
+                         float negative_slope, float dropout_p, uint64_t seed, const uint64_t* seed_used,
+                         float* grad_h, int64_t ld_grad_h, float* ds_src, int64_t ld_ds_src, float* dz,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int64_t ppgat_edge_dv_partial_rows(int64_t n_edges);
+int ppgat_edge_dv(const float* dz, const float* attr_csc, int64_t n_edges, int heads, int edge_dim, float* dv,
+                  float* part, void* stream);
+
 /* ---- loss of the training step ---------------------------------------------
  * Replaces: pos = (U[u]*I[i]).sum(-1); neg = (U[u]*I[j]).sum(-1); BPR
  *           -log(sigmoid(pos-neg)+1e-8).mean() (loss_kind 0) or BCE-with-logits over

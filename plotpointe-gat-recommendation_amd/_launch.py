@@ -35,15 +35,19 @@ def node_scores(h, att_src, att_dst, heads: int, channels: int, s_src, s_dst):
 
 
 def fwd(sched, col, csr_eid, n_edges: int, r0: int, n: int, h, s_src, s_dst, bias, heads: int, channels: int,
-        mode: int, slope, p, seed, seed_buf, out, m, inv_l, agg):
+        mode: int, slope, p, seed, seed_buf, out, m, inv_l, agg, edge_term=None):
     """The destination rows [r0, r0 + n) of ``sched`` (row ids relative to r0; edge slots and
-    source rows absolute): the destination-indexed tensors start at row r0."""
+    source rows absolute): the destination-indexed tensors start at row r0.  ``edge_term`` [E, H]
+    in CSR slot order: the edge-feature logit term (ppgat_edge_fwd)."""
     lib, dev = load(), h.device
     ws, nbytes = workspace(lib.ppgat_fwd_workspace_bytes, sched.n_hub_items, heads, channels, device=dev)
-    check(lib.ppgat_fwd(_sched(sched), *edge_ptrs(n_edges, col, csr_eid), n, n_edges, heads, channels, ptr(h),
-                        ptr(s_src), _at(s_dst, r0), ptr(bias), mode, float(slope), float(p), seed64(seed),
-                        ptr(seed_buf), _at(out, r0), _at(m, r0), _at(inv_l, r0), _at(agg, r0), ptr(ws), nbytes,
-                        stream_handle(dev)), "gat_fwd")
+    tail = (n, n_edges, heads, channels, ptr(h), ptr(s_src), _at(s_dst, r0), ptr(bias), mode, float(slope), float(p),
+            seed64(seed), ptr(seed_buf), _at(out, r0), _at(m, r0), _at(inv_l, r0), _at(agg, r0), ptr(ws), nbytes,
+            stream_handle(dev))
+    if edge_term is None:
+        check(lib.ppgat_fwd(_sched(sched), *edge_ptrs(n_edges, col, csr_eid), *tail), "gat_fwd")
+    else:
+        check(lib.ppgat_edge_fwd(_sched(sched), *edge_ptrs(n_edges, col, csr_eid, edge_term), *tail), "edge_fwd")
 
 
 def bwd_prologue(r0: int, n: int, grad_out, out, agg, bias, s_dst, m, inv_l, heads: int, channels: int, mode: int,
@@ -57,15 +61,40 @@ def bwd_prologue(r0: int, n: int, grad_out, out, agg, bias, s_dst, m, inv_l, hea
 
 
 def bwd_edges(sched, row, csc_eid, dz_slot, n_edges: int, r0: int, h, s_src, nstate, grad_out, heads: int,
-              channels: int, mode: int, slope, p, seed, seed_buf, D, S, dz):
+              channels: int, mode: int, slope, p, seed, seed_buf, D, S, dz, edge_term=None):
     """Pass B over the source rows of ``sched`` (row ids relative to r0; edge slots and destination
-    rows absolute): D and S from row r0 on, each with its own row stride; ``dz_slot`` None: dz in CSC order."""
+    rows absolute): D and S from row r0 on, each with its own row stride; ``dz_slot`` None: dz in CSC order.
+    ``edge_term`` [E, H] in CSC slot order: the edge-feature logit term (ppgat_edge_bwd_edges)."""
     lib, dev = load(), h.device
     ws, nbytes = workspace(lib.ppgat_fwd_workspace_bytes, sched.n_hub_items, heads, channels, device=dev)
-    check(lib.ppgat_bwd_edges(_sched(sched), *edge_ptrs(n_edges, row, csc_eid, dz_slot), n_edges, heads, channels,
-                              _at(h, r0), _at(s_src, r0), ptr(nstate), ptr(grad_out), mode, float(slope), float(p),
-                              seed64(seed), ptr(seed_buf), *row_ptr(D, r0), *row_ptr(S, r0), ptr(dz), ptr(ws),
-                              nbytes, stream_handle(dev)), "bwd_edges")
+    tail = (n_edges, heads, channels, _at(h, r0), _at(s_src, r0), ptr(nstate), ptr(grad_out), mode, float(slope),
+            float(p), seed64(seed), ptr(seed_buf), *row_ptr(D, r0), *row_ptr(S, r0), ptr(dz), ptr(ws), nbytes,
+            stream_handle(dev))
+    if edge_term is None:
+        check(lib.ppgat_bwd_edges(_sched(sched), *edge_ptrs(n_edges, row, csc_eid, dz_slot), *tail), "bwd_edges")
+    else:
+        check(lib.ppgat_edge_bwd_edges(_sched(sched), *edge_ptrs(n_edges, row, csc_eid, dz_slot, edge_term), *tail),
+              "edge_bwd_edges")
+
+
+def edge_attr_permute(edge_attr, slot_eid, n_edges: int, out):
+    """out [E, D] = edge_attr[slot_eid] (the staging of an attribute tensor into a view's slot order)."""
+    check(load().ppgat_edge_attr_permute(*edge_ptrs(n_edges, edge_attr, slot_eid), n_edges, edge_attr.size(1),
+                                         ptr(out), stream_handle(out.device)), "edge_attr_permute")
+
+
+def edge_terms(attr_csr, attr_csc, v, n_edges: int, heads: int, t_csr, t_csc):
+    """t_csr (and t_csc, when given) [E, H] from the staged attribute tables and v [H, D]."""
+    check(load().ppgat_edge_terms(*edge_ptrs(n_edges, attr_csr, attr_csc), ptr(v), n_edges, v.size(1), heads,
+                                  ptr(t_csr), ptr(t_csc), stream_handle(v.device)), "edge_terms")
+
+
+def edge_dv(dz, attr_csc, n_edges: int, heads: int, edge_dim: int, dv):
+    """dv [H, D] = dz^T attr_csc over the CSC slots (ordered block partials, no atomics)."""
+    lib, dev = load(), dv.device
+    part = _f32(max(int(lib.ppgat_edge_dv_partial_rows(n_edges)), 1) * heads * edge_dim, dev)
+    check(lib.ppgat_edge_dv(*edge_ptrs(n_edges, dz, attr_csc), n_edges, heads, edge_dim, ptr(dv), ptr(part),
+                            stream_handle(dev)), "edge_dv")
 
 
 def bwd_dst_sum(sched, n_dst: int, n_edges: int, heads: int, dz, csr2csc, out, csc: bool, all_long: bool = False):

@@ -111,6 +111,14 @@ SIGNATURES = {
                                  c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "ppgat_dynatt_bwd": (c_int, [SP, SP, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp,
                                  c_vp, c_vp, c_f, c_f, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "ppgat_edge_attr_permute": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_vp]),
+    "ppgat_edge_terms": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp]),
+    "ppgat_edge_fwd": (c_int, [SP, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_f,
+                               c_f, c_u64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "ppgat_edge_bwd_edges": (c_int, [SP, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int,
+                                     c_f, c_f, c_u64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
+    "ppgat_edge_dv_partial_rows": (c_i64, [c_i64]),
+    "ppgat_edge_dv": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp]),
     "ppgat_eval_sample": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_u64, c_vp, c_vp, c_vp]),
     "ppgat_sampled_rank": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "ppgat_full_rank_supported": (c_int, [c_int]),

@@ -6,6 +6,8 @@
                       ``forward(x, edge_index)``, and state_dict keys
                       (``lin.weight`` [H*C, F], ``att_src``/``att_dst`` [1, H, C],
                       ``bias`` [C]; the older ``lin_src.weight``/``lin_dst.weight`` keys load too).
+                      ``edge_dim=D`` (1..16) adds PyG's ``lin_edge.weight`` [H*C, D] and
+                      ``att_edge`` [1, H, C] and ``forward(x, edge_index, edge_attr)``.
 ``GATv2Conv``      -- torch_geometric.nn.GATv2Conv (dynamic attention) under the same options,
                       PyG's constructor names and state_dict keys (``att``, ``lin_l.*``,
                       ``lin_r.*``, ``bias``); runs as ``hip_ops.gatv2_aggregate`` after two
@@ -29,7 +31,8 @@ import math
 import torch
 
 from . import _lib
-from .hip_ops import gat_layer, gatv2_aggregate, gatv2_supported, graph_cache, join_rows, linear
+from .hip_ops import (EDGE_MAX_DIM, check_edge_attr, gat_layer, gatv2_aggregate, gatv2_supported, graph_cache,
+                      join_rows, linear)
 
 
 def _dropout_seed() -> int:
@@ -58,7 +61,11 @@ class GATConv(torch.nn.Module):
         if add_self_loops:
             raise NotImplementedError("GATConv(add_self_loops=True) not implemented; the reference passes False")
         if edge_dim is not None:
-            raise NotImplementedError("edge_dim (edge features) not implemented")
+            if int(edge_dim) < 1:
+                raise ValueError(f"edge_dim={edge_dim}: expected at least 1")
+            if int(edge_dim) > EDGE_MAX_DIM:
+                raise NotImplementedError(f"edge_dim={edge_dim} not implemented (edge_dim <= {EDGE_MAX_DIM})")
+            edge_dim = int(edge_dim)
         if residual:
             raise NotImplementedError("residual=True not implemented")
         if not _lib.load().ppgat_supported_channels(int(out_channels)):
@@ -67,11 +74,20 @@ class GATConv(torch.nn.Module):
             raise NotImplementedError("heads > 8 not implemented")
         self.in_channels, self.out_channels, self.heads = in_channels, out_channels, heads
         self.concat, self.negative_slope, self.dropout = concat, negative_slope, dropout
-        self.add_self_loops = add_self_loops
+        self.add_self_loops, self.edge_dim = add_self_loops, edge_dim
         self.lin = torch.nn.Linear(in_channels, heads * out_channels, bias=False)
         self.att_src = torch.nn.Parameter(torch.empty(1, heads, out_channels))
         self.att_dst = torch.nn.Parameter(torch.empty(1, heads, out_channels))
         self.bias = torch.nn.Parameter(torch.empty(out_channels)) if bias else None
+        # the edge parameters after the existing ones, created without drawing from the generator
+        # (reset_parameters initialises them last): a seeded construction gives the same lin /
+        # att_src / att_dst as the layer without edge_dim
+        if edge_dim is not None:
+            self.lin_edge = torch.nn.utils.skip_init(torch.nn.Linear, edge_dim, heads * out_channels, bias=False)
+            self.att_edge = torch.nn.Parameter(torch.empty(1, heads, out_channels))
+        else:
+            self.lin_edge = None
+            self.register_parameter("att_edge", None)
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -80,6 +96,9 @@ class GATConv(torch.nn.Module):
         _glorot_(self.att_dst)
         if self.bias is not None:
             torch.nn.init.zeros_(self.bias)
+        if self.lin_edge is not None:
+            _glorot_(self.lin_edge.weight)
+            _glorot_(self.att_edge)
 
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
                               error_msgs):
@@ -91,23 +110,43 @@ class GATConv(torch.nn.Module):
         super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
                                       error_msgs)
 
-    def forward(self, x: torch.Tensor, edge_index: torch.Tensor, return_attention_weights=None) -> torch.Tensor:
+    def _edge_args(self, edge_attr, n_edges: int, device) -> dict:
+        """gat_layer's edge arguments: ``edge_attr`` as the caller passed it (the staging cache keys
+        on that tensor object) and v [H, D], v[h, d] = sum_c att_edge[h, c] lin_edge.weight[h C + c, d]
+        -- an elementwise product and a sum, so autograd turns dv into both parameters' gradients."""
+        if edge_attr is None:  # PyG skips the term in the same way
+            return {}
+        if self.edge_dim is None:
+            raise ValueError("edge_attr given to a GATConv built without edge_dim")
+        check_edge_attr(edge_attr, n_edges, device)
+        D = 1 if edge_attr.dim() == 1 else edge_attr.size(1)
+        if D != self.edge_dim:
+            raise ValueError(f"edge_attr: {D} features per edge, but edge_dim={self.edge_dim}")
+        w = self.lin_edge.weight.view(self.heads, self.out_channels, self.edge_dim)
+        v = (w * self.att_edge.view(self.heads, self.out_channels, 1)).sum(1)
+        return {"edge_v": v, "edge_attr": edge_attr}
+
+    def forward(self, x: torch.Tensor, edge_index: torch.Tensor, edge_attr=None,
+                return_attention_weights=None) -> torch.Tensor:
         if return_attention_weights:
             raise NotImplementedError("return_attention_weights not implemented")
         graph = graph_cache.get(edge_index, x.size(0))
         p = float(self.dropout) if self.training else 0.0
         seed = _dropout_seed() if p > 0 else 0
         return gat_layer(x, self.lin.weight, self.att_src, self.att_dst, self.bias, graph, self.heads,
-                         self.out_channels, _lib.MODE_PYG, float(self.negative_slope), p, seed)
+                         self.out_channels, _lib.MODE_PYG, float(self.negative_slope), p, seed,
+                         **self._edge_args(edge_attr, graph.n_edges, x.device))
 
-    def forward_segments(self, x: torch.Tensor, x_items: torch.Tensor, edge_index: torch.Tensor) -> torch.Tensor:
-        """forward(cat(x, x_items), edge_index) without materialising the concatenation
+    def forward_segments(self, x: torch.Tensor, x_items: torch.Tensor, edge_index: torch.Tensor,
+                         edge_attr=None) -> torch.Tensor:
+        """forward(cat(x, x_items), edge_index, edge_attr) without materialising the concatenation
         (the model's node features, train_gat_pyg.py:79-82)."""
         graph = graph_cache.get(edge_index, x.size(0) + x_items.size(0))
         p = float(self.dropout) if self.training else 0.0
         seed = _dropout_seed() if p > 0 else 0
         return gat_layer(x, self.lin.weight, self.att_src, self.att_dst, self.bias, graph, self.heads,
-                         self.out_channels, _lib.MODE_PYG, float(self.negative_slope), p, seed, x_items=x_items)
+                         self.out_channels, _lib.MODE_PYG, float(self.negative_slope), p, seed, x_items=x_items,
+                         **self._edge_args(edge_attr, graph.n_edges, x.device))
 
     def __repr__(self):
         return (f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, heads={self.heads}, "

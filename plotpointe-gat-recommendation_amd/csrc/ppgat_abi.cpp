@@ -227,10 +227,12 @@ int ppgat_fwd_workspace_bytes(int64_t n_hub_items, int heads, int channels, size
   return PPGAT_OK;
 }
 
-int ppgat_fwd(const ppgat_schedule* sched, const int32_t* col, const int32_t* csr_eid, int64_t n_nodes,
-              int64_t n_edges, int heads, int channels, const float* h, const float* s_src, const float* s_dst,
-              const float* bias, int mode, float negative_slope, float dropout_p, uint64_t seed, uint64_t* seed_used,
-              float* out, float* m, float* inv_l, float* agg, void* workspace, size_t workspace_bytes, void* stream) {
+// ppgat_fwd, and ppgat_edge_fwd with the edge-feature logit term (edge_term NULL: none)
+static int fwd_impl(const ppgat_schedule* sched, const int32_t* col, const int32_t* csr_eid, const float* edge_term,
+                    int64_t n_nodes, int64_t n_edges, int heads, int channels, const float* h, const float* s_src,
+                    const float* s_dst, const float* bias, int mode, float negative_slope, float dropout_p,
+                    uint64_t seed, uint64_t* seed_used, float* out, float* m, float* inv_l, float* agg,
+                    void* workspace, size_t workspace_bytes, void* stream) {
   if (!channels_ok(channels)) return fail(PPGAT_ERR_UNSUPPORTED, "fwd: unsupported channels");
   if (heads < 1 || n_nodes < 0 || n_edges < 0) return fail(PPGAT_ERR_INVALID, "fwd: bad sizes");
   if (int rc = check_mode(mode, heads, bias, dropout_p)) return rc;
@@ -246,9 +248,28 @@ int ppgat_fwd(const ppgat_schedule* sched, const int32_t* col, const int32_t* cs
   Timed t(PPGAT_K_FWD, st);
   hipError_t e = ppgat::launch_fwd(*sched, col, csr_eid, heads, channels, h, s_src, s_dst, bias, mode, negative_slope,
                                    eps, dropout_p, seed, dropout_p > 0.f ? seed_used : nullptr, out, m, inv_l, agg,
-                                   static_cast<float*>(workspace), st);
+                                   static_cast<float*>(workspace), st, edge_term);
   if (e != hipSuccess) return hip_fail(e, "fwd");
   return PPGAT_OK;
+}
+
+int ppgat_fwd(const ppgat_schedule* sched, const int32_t* col, const int32_t* csr_eid, int64_t n_nodes,
+              int64_t n_edges, int heads, int channels, const float* h, const float* s_src, const float* s_dst,
+              const float* bias, int mode, float negative_slope, float dropout_p, uint64_t seed, uint64_t* seed_used,
+              float* out, float* m, float* inv_l, float* agg, void* workspace, size_t workspace_bytes, void* stream) {
+  return fwd_impl(sched, col, csr_eid, nullptr, n_nodes, n_edges, heads, channels, h, s_src, s_dst, bias, mode,
+                  negative_slope, dropout_p, seed, seed_used, out, m, inv_l, agg, workspace, workspace_bytes, stream);
+}
+
+int ppgat_edge_fwd(const ppgat_schedule* sched, const int32_t* col, const int32_t* csr_eid, const float* edge_term,
+                   int64_t n_nodes, int64_t n_edges, int heads, int channels, const float* h, const float* s_src,
+                   const float* s_dst, const float* bias, int mode, float negative_slope, float dropout_p,
+                   uint64_t seed, uint64_t* seed_used, float* out, float* m, float* inv_l, float* agg,
+                   void* workspace, size_t workspace_bytes, void* stream) {
+  if (n_edges > 0 && !edge_term) return fail(PPGAT_ERR_INVALID, "edge_fwd: null edge_term");
+  return fwd_impl(sched, col, csr_eid, n_edges > 0 ? edge_term : nullptr, n_nodes, n_edges, heads, channels, h,
+                  s_src, s_dst, bias, mode, negative_slope, dropout_p, seed, seed_used, out, m, inv_l, agg, workspace,
+                  workspace_bytes, stream);
 }
 
 // ---- backward, staged ---------------------------------------------------------------
@@ -279,12 +300,13 @@ int ppgat_bwd_prologue(const float* grad_out, const float* out, const float* agg
   return PPGAT_OK;
 }
 
-int ppgat_bwd_edges(const ppgat_schedule* src_sched, const int32_t* row, const int32_t* csc_eid,
-                    const int32_t* dz_slot, int64_t n_edges, int heads, int channels, const float* h,
-                    const float* s_src, const float* nstate, const float* grad_out, int mode, float negative_slope,
-                    float dropout_p, uint64_t seed, const uint64_t* seed_used, float* grad_h, int64_t ld_grad_h,
-                    float* ds_src, int64_t ld_ds_src, float* dz, void* workspace, size_t workspace_bytes,
-                    void* stream) {
+// ppgat_bwd_edges, and ppgat_edge_bwd_edges with the edge-feature logit term (edge_term NULL: none)
+static int bwd_edges_impl(const ppgat_schedule* src_sched, const int32_t* row, const int32_t* csc_eid,
+                          const int32_t* dz_slot, const float* edge_term, int64_t n_edges, int heads, int channels,
+                          const float* h, const float* s_src, const float* nstate, const float* grad_out, int mode,
+                          float negative_slope, float dropout_p, uint64_t seed, const uint64_t* seed_used,
+                          float* grad_h, int64_t ld_grad_h, float* ds_src, int64_t ld_ds_src, float* dz,
+                          void* workspace, size_t workspace_bytes, void* stream) {
   if (ld_grad_h < (int64_t)heads * channels || (ld_grad_h % 4) || ld_ds_src < heads)
     return fail(PPGAT_ERR_INVALID, "bwd_edges: bad leading dimensions (ld_grad_h >= H*C, multiple of 4)");
   if (!channels_ok(channels)) return fail(PPGAT_ERR_UNSUPPORTED, "bwd_edges: unsupported channels");
@@ -307,9 +329,75 @@ int ppgat_bwd_edges(const ppgat_schedule* src_sched, const int32_t* row, const i
     Timed t(PPGAT_K_BWD_SRC, st);
     e = ppgat::launch_bwd_src(*src_sched, row, csc_eid, dz_slot, heads, channels, h, s_src, nstate, grad_out, mode,
                               negative_slope, gscale, dropout_p, seed, seed_used, grad_h, ld_grad_h, ds_src, ld_ds_src,
-                              dz, static_cast<float*>(workspace), st);
+                              dz, static_cast<float*>(workspace), st, edge_term);
   }
   if (e != hipSuccess) return hip_fail(e, "bwd_edges");
+  return PPGAT_OK;
+}
+
+int ppgat_bwd_edges(const ppgat_schedule* src_sched, const int32_t* row, const int32_t* csc_eid,
+                    const int32_t* dz_slot, int64_t n_edges, int heads, int channels, const float* h,
+                    const float* s_src, const float* nstate, const float* grad_out, int mode, float negative_slope,
+                    float dropout_p, uint64_t seed, const uint64_t* seed_used, float* grad_h, int64_t ld_grad_h,
+                    float* ds_src, int64_t ld_ds_src, float* dz, void* workspace, size_t workspace_bytes,
+                    void* stream) {
+  return bwd_edges_impl(src_sched, row, csc_eid, dz_slot, nullptr, n_edges, heads, channels, h, s_src, nstate,
+                        grad_out, mode, negative_slope, dropout_p, seed, seed_used, grad_h, ld_grad_h, ds_src,
+                        ld_ds_src, dz, workspace, workspace_bytes, stream);
+}
+
+int ppgat_edge_bwd_edges(const ppgat_schedule* src_sched, const int32_t* row, const int32_t* csc_eid,
+                         const int32_t* dz_slot, const float* edge_term, int64_t n_edges, int heads, int channels,
+                         const float* h, const float* s_src, const float* nstate, const float* grad_out, int mode,
+                         float negative_slope, float dropout_p, uint64_t seed, const uint64_t* seed_used,
+                         float* grad_h, int64_t ld_grad_h, float* ds_src, int64_t ld_ds_src, float* dz,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+  if (n_edges > 0 && !edge_term) return fail(PPGAT_ERR_INVALID, "edge_bwd_edges: null edge_term");
+  return bwd_edges_impl(src_sched, row, csc_eid, dz_slot, n_edges > 0 ? edge_term : nullptr, n_edges, heads, channels,
+                        h, s_src, nstate, grad_out, mode, negative_slope, dropout_p, seed, seed_used, grad_h,
+                        ld_grad_h, ds_src, ld_ds_src, dz, workspace, workspace_bytes, stream);
+}
+
+// ---- edge features: staging, per-step terms, dv ---------------------------------------
+static_assert(PPGAT_EDGE_MAX_DIM == 16, "edge feature width bound (ppgat_egat.hip kEdgeMaxD)");
+
+int ppgat_edge_attr_permute(const float* edge_attr, const int32_t* slot_eid, int64_t n_edges, int edge_dim,
+                            float* out, void* stream) {
+  if (n_edges < 0 || n_edges >= ((int64_t)1 << 31))  // int32 edge ids
+    return fail(PPGAT_ERR_INVALID, "edge_attr_permute: bad n_edges");
+  if (edge_dim < 1) return fail(PPGAT_ERR_INVALID, "edge_attr_permute: edge_dim < 1");
+  if (edge_dim > PPGAT_EDGE_MAX_DIM) return fail(PPGAT_ERR_UNSUPPORTED, "edge_attr_permute: edge_dim > 16");
+  if (n_edges > 0 && (!edge_attr || !slot_eid || !out)) return fail(PPGAT_ERR_INVALID, "edge_attr_permute: null pointer");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = debug_range(slot_eid, 4, n_edges, 0, n_edges, "edge_attr_permute: slot_eid", st)) return rc;
+  hipError_t e = ppgat::edge_attr_permute(edge_attr, slot_eid, n_edges, edge_dim, out, st);
+  if (e != hipSuccess) return hip_fail(e, "edge_attr_permute");
+  return PPGAT_OK;
+}
+
+int ppgat_edge_terms(const float* attr_csr, const float* attr_csc, const float* v, int64_t n_edges, int edge_dim,
+                     int heads, float* t_csr, float* t_csc, void* stream) {
+  if (n_edges < 0 || heads < 1 || heads > ppgat::kMaxHeads || edge_dim < 1)
+    return fail(PPGAT_ERR_INVALID, "edge_terms: bad sizes");
+  if (edge_dim > PPGAT_EDGE_MAX_DIM) return fail(PPGAT_ERR_UNSUPPORTED, "edge_terms: edge_dim > 16");
+  if (n_edges > 0 && (!attr_csr || !v || !t_csr || (t_csc && !attr_csc)))
+    return fail(PPGAT_ERR_INVALID, "edge_terms: null pointer");
+  hipError_t e = ppgat::edge_terms(attr_csr, attr_csc, v, n_edges, edge_dim, heads, t_csr, t_csc,
+                                   static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail(e, "edge_terms");
+  return PPGAT_OK;
+}
+
+int64_t ppgat_edge_dv_partial_rows(int64_t n_edges) { return n_edges < 0 ? -1 : ppgat::edge_dv_blocks(n_edges); }
+
+int ppgat_edge_dv(const float* dz, const float* attr_csc, int64_t n_edges, int heads, int edge_dim, float* dv,
+                  float* part, void* stream) {
+  if (n_edges < 0 || heads < 1 || heads > ppgat::kMaxHeads || edge_dim < 1)
+    return fail(PPGAT_ERR_INVALID, "edge_dv: bad sizes");
+  if (edge_dim > PPGAT_EDGE_MAX_DIM) return fail(PPGAT_ERR_UNSUPPORTED, "edge_dv: edge_dim > 16");
+  if (!dv || !part || (n_edges > 0 && (!dz || !attr_csc))) return fail(PPGAT_ERR_INVALID, "edge_dv: null pointer");
+  hipError_t e = ppgat::edge_dv(dz, attr_csc, n_edges, heads, edge_dim, dv, part, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail(e, "edge_dv");
   return PPGAT_OK;
 }
 

@@ -23,7 +23,7 @@ hipError_t launch_scores(const float* h, const float* as, const float* ad, int64
 hipError_t launch_fwd(const ppgat_schedule& sch, const int32_t* col, const int32_t* eid, int heads, int C,
                       const float* h, const float* ss, const float* sd, const float* bias, int mode, float slope,
                       float eps, float p, uint64_t seed, uint64_t* seed_out, float* out, float* m, float* invl,
-                      float* agg, float* partial, hipStream_t st);
+                      float* agg, float* partial, hipStream_t st, const float* et = nullptr);
 hipError_t launch_bwd_pro(const float* go, const float* out, const float* agg, const float* bias, const float* sd,
                           const float* m, const float* invl, int64_t n, int heads, int C, float gscale,
                           float* nstate, float* bias_part, int64_t blocks, hipStream_t st);
@@ -31,7 +31,14 @@ hipError_t launch_bwd_src(const ppgat_schedule& sch, const int32_t* row, const i
                           int heads, int C, const float* h, const float* ss, const float* nstate, const float* go,
                           int mode, float slope, float gscale, float p, uint64_t seed, const uint64_t* seed_in,
                           float* dh, int64_t ld_dh, float* ds_src, int64_t ld_ds, float* dz, float* partial,
-                          hipStream_t st);
+                          hipStream_t st, const float* et = nullptr);
+// edge features (ppgat_egat.hip): attribute staging, per-step logit terms, the dv reduction
+hipError_t edge_attr_permute(const float* attr, const int32_t* eid, int64_t E, int D, float* out, hipStream_t st);
+hipError_t edge_terms(const float* attr_csr, const float* attr_csc, const float* v, int64_t E, int D, int H,
+                      float* t_csr, float* t_csc, hipStream_t st);
+int64_t edge_dv_blocks(int64_t E);
+hipError_t edge_dv(const float* dz, const float* attr, int64_t E, int H, int D, float* dv, float* part,
+                   hipStream_t st);
 hipError_t launch_dst_sum(const ppgat_schedule& sch, int heads, const float* dz, const int32_t* csr2csc, float* ds_dst,
                           int64_t ld, float* partial, hipStream_t st);
 hipError_t launch_invert_index(const int32_t* p, int64_t n, int32_t* inv, hipStream_t st);

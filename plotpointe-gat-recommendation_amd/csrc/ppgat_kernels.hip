@@ -113,7 +113,9 @@ __global__ void __launch_bounds__(256) k_scores(const float* __restrict__ h, con
 //   acc = sum_k exp(e_k - m) * d_k * h[j]  (d_k = dropout multiplier)
 // partial slab (hub pieces) per (item, head): [acc C | m | l | pad pad]
 // ---------------------------------------------------------------------------
-template <int C>
+// EDGE: the edge-feature logit term et [E, H] in CSR slot order (ppgat_edge_terms) joins the
+// logit as (s_src[j] + s_dst[i]) + et[k] -- that association order in forward and pass B.
+template <int C, bool EDGE = false>
 __global__ void __launch_bounds__(256) k_fwd(Items it, const int32_t* __restrict__ col,
                                              const int32_t* __restrict__ eid, int heads,
                                              const float* __restrict__ h, const float* __restrict__ s_src,
@@ -121,7 +123,8 @@ __global__ void __launch_bounds__(256) k_fwd(Items it, const int32_t* __restrict
                                              int mode, float slope, float eps, float p, float inv_keep,
                                              uint64_t seed, float* __restrict__ out, float* __restrict__ m_out,
                                              float* __restrict__ invl_out, float* __restrict__ agg_out,
-                                             float* __restrict__ partial, uint64_t* __restrict__ seed_out) {
+                                             float* __restrict__ partial, uint64_t* __restrict__ seed_out,
+                                             const float* __restrict__ et) {
   if (p > 0.f) seed = epoch_seed(seed);
   if (seed_out != nullptr && blockIdx.x == 0 && threadIdx.x == 0) seed_out[0] = seed;  // the backward's mask seed
   using G = Geo<C>;
@@ -144,7 +147,11 @@ __global__ void __launch_bounds__(256) k_fwd(Items it, const int32_t* __restrict
       const bool valid = k < re;
       const int j = valid ? col[k] : 0;
       float e = -INFINITY;
-      if (valid) e = logit(s_src[(int64_t)j * heads + hd] + sd, slope, mode);
+      if (valid) {
+        float z = s_src[(int64_t)j * heads + hd] + sd;
+        if constexpr (EDGE) z += et[(int64_t)k * heads + hd];
+        e = logit(z, slope, mode);
+      }
       float pe;
       if (pyg) {
         const float mn = fmaxf(m, wave_max(e));
@@ -228,7 +235,7 @@ struct HubMerge {
   int64_t mblocks;
 };
 
-template <int C>
+template <int C, bool EDGE = false>
 __global__ void __launch_bounds__(256) k_fwd_short(Items it, int64_t first, const int32_t* __restrict__ col,
                                                    const int32_t* __restrict__ eid, const float* __restrict__ h,
                                                    const float* __restrict__ s_src, const float* __restrict__ s_dst,
@@ -236,7 +243,7 @@ __global__ void __launch_bounds__(256) k_fwd_short(Items it, int64_t first, cons
                                                    float p, float inv_keep, uint64_t seed, float* __restrict__ out,
                                                    float* __restrict__ m_out, float* __restrict__ invl_out,
                                                    float* __restrict__ agg_out, uint64_t* __restrict__ seed_out,
-                                                   HubMerge mg) {
+                                                   HubMerge mg, const float* __restrict__ et) {
   if (p > 0.f) seed = epoch_seed(seed);
   if (seed_out != nullptr && blockIdx.x == 0 && threadIdx.x == 0) seed_out[0] = seed;  // the backward's mask seed
   constexpr int NV = C / 64;  // float4 columns per lane
@@ -260,7 +267,12 @@ __global__ void __launch_bounds__(256) k_fwd_short(Items it, int64_t first, cons
   const int k = rs + ql;
   const bool valid = k < re;
   const int j = valid ? col[k] : 0;
-  const float e = valid ? logit(s_src[j] + s_dst[i], slope, mode) : -INFINITY;
+  float e = -INFINITY;
+  if (valid) {
+    float z = s_src[j] + s_dst[i];
+    if constexpr (EDGE) z += et[k];
+    e = logit(z, slope, mode);
+  }
   float m = 0.f, pe;
   if (pyg) {
     m = group_reduce<Op::Max, 1, 8>(e);
@@ -449,7 +461,7 @@ __global__ void __launch_bounds__(256) k_bwd_pro(const float* __restrict__ grad_
 // alpha is recomputed from the saved (m, inv_l): nothing [E]-sized was saved.
 // hub-piece partial slab per (item, head): [dh C | ds | pad pad pad]
 // ---------------------------------------------------------------------------
-template <int C>
+template <int C, bool EDGE = false>
 __global__ void __launch_bounds__(256) k_bwd_src(Items it, const int32_t* __restrict__ row,
                                                  const int32_t* __restrict__ csc_eid,
                                                  const int32_t* __restrict__ csc2csr, int heads,
@@ -459,7 +471,8 @@ __global__ void __launch_bounds__(256) k_bwd_src(Items it, const int32_t* __rest
                                                  float gscale, float p, float inv_keep, uint64_t seed,
     const uint64_t* __restrict__ seed_in,
                                                  float* __restrict__ dh, int64_t ld_dh, float* __restrict__ ds_src,
-                                                 int64_t ld_ds, float* __restrict__ dz, float* __restrict__ partial) {
+                                                 int64_t ld_ds, float* __restrict__ dz, float* __restrict__ partial,
+                                                 const float* __restrict__ et) {
   if (p > 0.f) seed = seed_in != nullptr ? *seed_in : epoch_seed(seed);
   using G = Geo<C>;
   constexpr int GRP = G::LPR / G::U;  // lanes sharing one reduced edge value
@@ -489,7 +502,8 @@ __global__ void __launch_bounds__(256) k_bwd_src(Items it, const int32_t* __rest
       int slot = 0;
       if (valid) {
         const float4 st = nstate[(int64_t)i * heads + hd];  // {s_dst, m, inv_l, D}
-        const float z = ss + st.x;
+        float z = ss + st.x;
+        if constexpr (EDGE) z += et[(int64_t)k * heads + hd];  // et in CSC slot order
         const float e = logit(z, slope, mode);
         const float af = expf(e - st.y) * st.z;
         const float dm = p > 0.f ? drop_scale(seed, (uint32_t)csc_eid[k], (uint32_t)hd, p, inv_keep) : 1.f;
@@ -551,7 +565,7 @@ __device__ __forceinline__ void bwd_merge_wave(int64_t hb, const int32_t* __rest
                                                const float* __restrict__ partial, float* __restrict__ dh,
                                                int64_t ld_dh, float* __restrict__ ds_src, int64_t ld_ds);
 
-template <int C>
+template <int C, bool EDGE = false>
 __global__ void __launch_bounds__(256) k_bwd_src_short(Items it, int64_t first, const int32_t* __restrict__ row,
                                                        const int32_t* __restrict__ csc_eid,
                                                        const int32_t* __restrict__ csc2csr,
@@ -562,7 +576,8 @@ __global__ void __launch_bounds__(256) k_bwd_src_short(Items it, int64_t first, 
     const uint64_t* __restrict__ seed_in,
                                                        float* __restrict__ dh, int64_t ld_dh,
                                                        float* __restrict__ ds_src, int64_t ld_ds,
-                                                       float* __restrict__ dz, HubMerge mg) {
+                                                       float* __restrict__ dz, HubMerge mg,
+                                                       const float* __restrict__ et) {
   if (p > 0.f) seed = seed_in != nullptr ? *seed_in : epoch_seed(seed);
   constexpr int NV = C / 64;
   static_assert(NV >= 1, "k_bwd_src_short: C >= 64");
@@ -590,7 +605,8 @@ __global__ void __launch_bounds__(256) k_bwd_src_short(Items it, int64_t first, 
   int slot = 0;
   if (valid) {
     const float4 st = nstate[i];  // {s_dst, m, inv_l, D}
-    const float z = ss + st.x;
+    float z = ss + st.x;
+    if constexpr (EDGE) z += et[k];  // et in CSC slot order
     const float af = expf(logit(z, slope, mode) - st.y) * st.z;
     const float dm = p > 0.f ? drop_scale(seed, (uint32_t)csc_eid[k], 0u, p, inv_keep) : 1.f;
     slot = csc2csr != nullptr ? csc2csr[k] : k;  // NULL: dz in CSC order
@@ -685,7 +701,7 @@ __device__ __forceinline__ int mh_transpose(float (&v)[16], int sl, int& base) {
   }
 }
 
-template <int C, int H>
+template <int C, int H, bool EDGE = false>
 __global__ void __launch_bounds__(256) k_bwd_src_mh(Items it, const int32_t* __restrict__ row,
                                                     const int32_t* __restrict__ csc_eid,
                                                     const int32_t* __restrict__ csc2csr,
@@ -695,7 +711,8 @@ __global__ void __launch_bounds__(256) k_bwd_src_mh(Items it, const int32_t* __r
                                                     float gscale, float p, float inv_keep, uint64_t seed,
     const uint64_t* __restrict__ seed_in,
                                                     float* __restrict__ dh, int64_t ld_dh, float* __restrict__ ds_src,
-                                                    int64_t ld_ds, float* __restrict__ dz, float* __restrict__ partial) {
+                                                    int64_t ld_ds, float* __restrict__ dz, float* __restrict__ partial,
+                                                    const float* __restrict__ et) {
   if (p > 0.f) seed = seed_in != nullptr ? *seed_in : epoch_seed(seed);
   using G = Geo<C>;
   static_assert(C >= 32, "k_bwd_src_mh: C >= 32");
@@ -733,7 +750,8 @@ __global__ void __launch_bounds__(256) k_bwd_src_mh(Items it, const int32_t* __r
       float bg = 0.f, c1 = 0.f, c0 = 0.f;
       if (valid) {
         const float4 st = nstate[(int64_t)i * H + hd];  // {s_dst, m, inv_l, D}
-        const float z = ss[hd] + st.x;
+        float z = ss[hd] + st.x;
+        if constexpr (EDGE) z += et[(int64_t)k * H + hd];  // et in CSC slot order
         const float e = logit(z, slope, mode);
         const float af = expf(e - st.y) * st.z;
         const float dm = p > 0.f ? drop_scale(seed, eid, (uint32_t)hd, p, inv_keep) : 1.f;
@@ -1119,7 +1137,7 @@ static int64_t short_begin(const ppgat_schedule& sch, int heads, int C) {
 hipError_t launch_fwd(const ppgat_schedule& sch, const int32_t* col, const int32_t* eid, int heads, int C,
                       const float* h, const float* ss, const float* sd, const float* bias, int mode, float slope,
                       float eps, float p, uint64_t seed, uint64_t* seed_out, float* out, float* m, float* invl,
-                      float* agg, float* partial, hipStream_t st) {
+                      float* agg, float* partial, hipStream_t st, const float* et) {
   const float inv_keep = p > 0.f ? 1.f / (1.f - p) : 1.f;
   // the effective mask seed is written by block 0 of the first edge kernel launched (no
   // separate launch); a graph without items snapshots it with k_seed_snap
@@ -1127,9 +1145,15 @@ hipError_t launch_fwd(const ppgat_schedule& sch, const int32_t* col, const int32
   const Items its = items_of(sch, n_long);
   if (seed_out != nullptr && sch.n_items == 0) hipLaunchKernelGGL(k_seed_snap, dim3(1), dim3(64), 0, st, seed, seed_out);
   if (n_long > 0) {
-    PPGAT_DISPATCH_C(C, hipLaunchKernelGGL(k_fwd<CC>, dim3(blocks_for(n_long * 64)), dim3(256), 0, st, its, col,
-                                           eid, heads, h, ss, sd, bias, mode, slope, eps, p, inv_keep, seed, out, m,
-                                           invl, agg, partial, seed_out));
+    if (et != nullptr) {
+      PPGAT_DISPATCH_C(C, hipLaunchKernelGGL((k_fwd<CC, true>), dim3(blocks_for(n_long * 64)), dim3(256), 0, st, its,
+                                             col, eid, heads, h, ss, sd, bias, mode, slope, eps, p, inv_keep, seed,
+                                             out, m, invl, agg, partial, seed_out, et));
+    } else {
+      PPGAT_DISPATCH_C(C, hipLaunchKernelGGL(k_fwd<CC>, dim3(blocks_for(n_long * 64)), dim3(256), 0, st, its, col,
+                                             eid, heads, h, ss, sd, bias, mode, slope, eps, p, inv_keep, seed, out, m,
+                                             invl, agg, partial, seed_out, et));
+    }
   }
   // the hub merges ride at the head of the short-item launch when there is one (one launch fewer)
   const bool fold = n_long < sch.n_items;
@@ -1137,9 +1161,14 @@ hipError_t launch_fwd(const ppgat_schedule& sch, const int32_t* col, const int32
     const Items all = items_of(sch, sch.n_items);
     const HubMerge mg{sch.hub_row, sch.hub_ptr, sch.n_hubs, heads, partial, sch.n_hubs > 0 ? (sch.n_hubs + 3) / 4 : 0};
     const unsigned g = (unsigned)((sch.n_items - n_long + 15) / 16 + mg.mblocks);  // 4 waves x 4 items per block
-    PPGAT_DISPATCH_C64(C, hipLaunchKernelGGL(k_fwd_short<CC>, dim3(g), dim3(256), 0, st, all, n_long, col, eid, h,
-                                             ss, sd, bias, mode, slope, eps, p, inv_keep, seed, out, m, invl, agg,
-                                             n_long > 0 ? nullptr : seed_out, mg));
+    if (et != nullptr)
+      PPGAT_DISPATCH_C64(C, hipLaunchKernelGGL((k_fwd_short<CC, true>), dim3(g), dim3(256), 0, st, all, n_long, col,
+                                               eid, h, ss, sd, bias, mode, slope, eps, p, inv_keep, seed, out, m, invl,
+                                               agg, n_long > 0 ? nullptr : seed_out, mg, et));
+    else
+      PPGAT_DISPATCH_C64(C, hipLaunchKernelGGL(k_fwd_short<CC>, dim3(g), dim3(256), 0, st, all, n_long, col, eid, h,
+                                               ss, sd, bias, mode, slope, eps, p, inv_keep, seed, out, m, invl, agg,
+                                               n_long > 0 ? nullptr : seed_out, mg, et));
   }
   if (sch.n_hubs > 0 && !fold) {
     PPGAT_DISPATCH_C(C, hipLaunchKernelGGL(k_fwd_merge<CC>, dim3(blocks_for(sch.n_hubs * 64)), dim3(256), 0, st,
@@ -1163,26 +1192,39 @@ hipError_t launch_bwd_src(const ppgat_schedule& sch, const int32_t* row, const i
                           int heads, int C, const float* h, const float* ss, const float* nstate, const float* go,
                           int mode, float slope, float gscale, float p, uint64_t seed, const uint64_t* seed_in,
                           float* dh, int64_t ld_dh, float* ds_src, int64_t ld_ds, float* dz, float* partial,
-                          hipStream_t st) {
+                          hipStream_t st, const float* et) {
   const float inv_keep = p > 0.f ? 1.f / (1.f - p) : 1.f;
   const int64_t n_long = short_begin(sch, heads, C);
   const Items its = items_of(sch, n_long);
   if (n_long > 0) {
     const bool mh = heads > 1 && C >= 32 && (heads == 2 || heads == 4 || heads == 8);
     if (mh) {  // every head of an edge in one pass (one grad_out gather per edge)
-#define PPGAT_MH(HH)                                                                                           \
+#define PPGAT_MH_E(HH, EE)                                                                                     \
   PPGAT_DISPATCH_C(C, if constexpr (CC >= 32) {                                                             \
-    hipLaunchKernelGGL((k_bwd_src_mh<CC, HH>), dim3(blocks_for(n_long * 64)), dim3(256), 0, st, its, row,      \
+    hipLaunchKernelGGL((k_bwd_src_mh<CC, HH, EE>), dim3(blocks_for(n_long * 64)), dim3(256), 0, st, its, row,  \
                        csc_eid, csc2csr, h, ss, reinterpret_cast<const float4*>(nstate), go, mode, slope, gscale, \
-                       p, inv_keep, seed, seed_in, dh, ld_dh, ds_src, ld_ds, dz, partial);                    \
+                       p, inv_keep, seed, seed_in, dh, ld_dh, ds_src, ld_ds, dz, partial, et);                \
   })
+#define PPGAT_MH(HH)                        \
+  do {                                      \
+    if (et != nullptr) { PPGAT_MH_E(HH, true); } \
+    else { PPGAT_MH_E(HH, false); }         \
+  } while (0)
       if (heads == 2) { PPGAT_MH(2); } else if (heads == 4) { PPGAT_MH(4); } else { PPGAT_MH(8); }
 #undef PPGAT_MH
+#undef PPGAT_MH_E
     } else {
-      PPGAT_DISPATCH_C(C, hipLaunchKernelGGL(k_bwd_src<CC>, dim3(blocks_for(n_long * 64)), dim3(256), 0, st, its,
-                                             row, csc_eid, csc2csr, heads, h, ss,
-                                             reinterpret_cast<const float4*>(nstate), go, mode, slope, gscale, p,
-                                             inv_keep, seed, seed_in, dh, ld_dh, ds_src, ld_ds, dz, partial));
+      if (et != nullptr) {
+        PPGAT_DISPATCH_C(C, hipLaunchKernelGGL((k_bwd_src<CC, true>), dim3(blocks_for(n_long * 64)), dim3(256), 0, st,
+                                               its, row, csc_eid, csc2csr, heads, h, ss,
+                                               reinterpret_cast<const float4*>(nstate), go, mode, slope, gscale, p,
+                                               inv_keep, seed, seed_in, dh, ld_dh, ds_src, ld_ds, dz, partial, et));
+      } else {
+        PPGAT_DISPATCH_C(C, hipLaunchKernelGGL(k_bwd_src<CC>, dim3(blocks_for(n_long * 64)), dim3(256), 0, st, its,
+                                               row, csc_eid, csc2csr, heads, h, ss,
+                                               reinterpret_cast<const float4*>(nstate), go, mode, slope, gscale, p,
+                                               inv_keep, seed, seed_in, dh, ld_dh, ds_src, ld_ds, dz, partial, et));
+      }
     }
   }
   // the short items after the long ones, with the hub merges at the head of that launch
@@ -1191,10 +1233,16 @@ hipError_t launch_bwd_src(const ppgat_schedule& sch, const int32_t* row, const i
     const Items all = items_of(sch, sch.n_items);
     const HubMerge mg{sch.hub_row, sch.hub_ptr, sch.n_hubs, heads, partial, sch.n_hubs > 0 ? (sch.n_hubs + 3) / 4 : 0};
     const unsigned g = (unsigned)((sch.n_items - n_long + 15) / 16 + mg.mblocks);
-    PPGAT_DISPATCH_C64(C, hipLaunchKernelGGL(k_bwd_src_short<CC>, dim3(g), dim3(256), 0, st, all, n_long, row,
-                                             csc_eid, csc2csr, h, ss, reinterpret_cast<const float4*>(nstate), go,
-                                             mode, slope, gscale, p, inv_keep, seed, seed_in, dh, ld_dh, ds_src, ld_ds,
-                                             dz, mg));
+    if (et != nullptr)
+      PPGAT_DISPATCH_C64(C, hipLaunchKernelGGL((k_bwd_src_short<CC, true>), dim3(g), dim3(256), 0, st, all, n_long, row,
+                                               csc_eid, csc2csr, h, ss, reinterpret_cast<const float4*>(nstate), go,
+                                               mode, slope, gscale, p, inv_keep, seed, seed_in, dh, ld_dh, ds_src,
+                                               ld_ds, dz, mg, et));
+    else
+      PPGAT_DISPATCH_C64(C, hipLaunchKernelGGL(k_bwd_src_short<CC>, dim3(g), dim3(256), 0, st, all, n_long, row,
+                                               csc_eid, csc2csr, h, ss, reinterpret_cast<const float4*>(nstate), go,
+                                               mode, slope, gscale, p, inv_keep, seed, seed_in, dh, ld_dh, ds_src,
+                                               ld_ds, dz, mg, et));
   }
   if (sch.n_hubs > 0 && !fold) {
     PPGAT_DISPATCH_C(C, hipLaunchKernelGGL(k_bwd_merge<CC>, dim3(blocks_for(sch.n_hubs * 64)), dim3(256), 0, st,

@@ -199,6 +199,50 @@ def build_edge_index(n_users: int, n_items: int, train_pos_idx: Dict[int, np.nda
     return torch.from_numpy(edge_index_numpy(n_users, users, items))
 
 
+def edge_attr_rating(train_pos_idx: Dict[int, np.ndarray], interactions=None, user_to_idx=None,
+                     item_to_idx=None) -> np.ndarray:
+    """Rating edge features for ``build_edge_index(n_users, n_items, train_pos_idx)``: float32 [E, 1]
+    whose columns 2t and 2t + 1 (the two directions of train interaction t, in build_edge_index's
+    order: users in dict order, each user's items in list order) carry (r_t - 1) / 4 -- the rating
+    weight of ``build_ui_edges``; 1.0 where there is no rating column (or no interactions frame).
+    ``interactions``: the frame the splits were built from, ``user_to_idx`` / ``item_to_idx`` the
+    node maps behind ``train_pos_idx``.  A (user, item) pair that occurs more than once is matched
+    in (ts, row) order, the order ``build_splits`` lists a user's items in.  Vectorised: one stable
+    sort of the frame's pairs and one of the train pairs."""
+    T = int(sum(len(v) for v in train_pos_idx.values()))
+    if interactions is None or "rating" not in interactions.columns:
+        return np.ones((2 * T, 1), dtype=np.float32)
+    order = np.lexsort((np.arange(len(interactions)), interactions["ts"].to_numpy()))
+    df = interactions.iloc[order]
+    uu = df["user_id"].astype(str).map(user_to_idx).to_numpy(dtype=np.float64, na_value=np.nan)
+    ii = df["asin"].astype(str).map(item_to_idx).to_numpy(dtype=np.float64, na_value=np.nan)
+    ok = ~(np.isnan(uu) | np.isnan(ii))  # both ends mapped
+    uu, ii, rr = uu[ok].astype(np.int64), ii[ok].astype(np.int64), df["rating"].to_numpy(dtype=np.float64)[ok]
+    if T == 0:
+        return np.zeros((0, 1), dtype=np.float32)
+    keys = list(train_pos_idx.keys())
+    lens = np.fromiter((len(train_pos_idx[k]) for k in keys), dtype=np.int64, count=len(keys))
+    tu = np.repeat(np.asarray(keys, dtype=np.int64), lens)
+    ti = np.concatenate([np.asarray(train_pos_idx[k], dtype=np.int64) for k in keys])
+    M = int(max(ii.max(initial=0), ti.max(initial=0))) + 1
+    # a join on (pair, running count of the pair): the frame's pairs sorted stably, so a pair's
+    # occurrences stay in (ts, row) order; train occurrence r of a pair is the frame's occurrence r
+    fkey = uu * M + ii
+    forder = np.argsort(fkey, kind="stable")
+    fsorted = fkey[forder]
+    tkey = tu * M + ti
+    torder = np.argsort(tkey, kind="stable")
+    tsorted = tkey[torder]
+    first = np.flatnonzero(np.r_[True, tsorted[1:] != tsorted[:-1]])
+    rank = np.empty(T, dtype=np.int64)
+    rank[torder] = np.arange(T) - np.repeat(first, np.diff(np.r_[first, T]))
+    pos = np.searchsorted(fsorted, tkey, side="left") + rank
+    if len(fsorted) == 0 or bool((pos >= len(fsorted)).any()) or not np.array_equal(fsorted[np.minimum(pos, len(fsorted) - 1)], tkey):
+        raise KeyError("edge_attr_rating: a train interaction is not in the interactions frame")
+    w = rr[forder][pos]
+    return np.repeat(((w - 1.0) / 4.0).astype(np.float32), 2).reshape(2 * T, 1)
+
+
 def sample_bpr_epoch(train_pos_idx: Dict[int, np.ndarray], n_items: int, samples: int):
     """scripts/train_gat_pyg.py:179-190 -- same Python ``random`` draw sequence,
     so a seeded run yields the reference's exact triples."""

@@ -103,12 +103,18 @@ def metrics_from_ranks(ranks: np.ndarray, Ks: Sequence[int] = (10, 20)) -> Dict[
     return {m: float(np.mean(v)) if v else 0.0 for m, v in metrics.items()}
 
 
+def _edge_kw(edge_attr) -> dict:
+    """The model forward's edge argument (only models built with edge_dim take one)."""
+    return {} if edge_attr is None else {"edge_attr": edge_attr}
+
+
 def eval_sampled(model, cfg, item_feats: torch.Tensor, edge_index: torch.Tensor,
                  train_pos_idx: Dict[int, np.ndarray], eval_pos: Dict[int, int], Ks=(10, 20), fast: bool = False,
-                 sampler=None, seed: int = 0):
-    """Mirror of eval_sampled (train_gat_pyg.py:150-176); ``cfg.eval_neg_k`` negatives."""
+                 sampler=None, seed: int = 0, edge_attr=None):
+    """Mirror of eval_sampled (train_gat_pyg.py:150-176); ``cfg.eval_neg_k`` negatives.
+    ``edge_attr``: the edge features of a model built with edge_dim (here and in the functions below)."""
     with torch.no_grad():
-        Z = model(item_feats, edge_index)
+        Z = model(item_feats, edge_index, **_edge_kw(edge_attr))
     if sampler is not None:
         if not eval_pos:
             return metrics_from_ranks(np.zeros(0, np.int64), Ks)
@@ -168,13 +174,14 @@ def full_rank(Z_users: torch.Tensor, Z_items: torch.Tensor, users, pos, sampler=
 
 
 def eval_full(model, cfg, item_feats: torch.Tensor, edge_index: torch.Tensor,
-              train_pos_idx: Dict[int, np.ndarray], eval_pos: Dict[int, int], Ks=(10, 20), sampler=None):
+              train_pos_idx: Dict[int, np.ndarray], eval_pos: Dict[int, int], Ks=(10, 20), sampler=None,
+              edge_attr=None):
     """eval_sampled's call shape and returned dict, under the full-ranking protocol: each held-out
     positive is ranked against every item outside the user's train history (``full_rank``).
     ``sampler``: a sampler.BPRSampler over the train lists; None builds one from
     ``train_pos_idx``.  ``cfg`` is unused (no negatives are drawn)."""
     with torch.no_grad():
-        Z = model(item_feats, edge_index)
+        Z = model(item_feats, edge_index, **_edge_kw(edge_attr))
     if not eval_pos:
         return metrics_from_ranks(np.zeros(0, np.int64), Ks)
     n_users, n_items = model.n_users, model.n_items
@@ -297,13 +304,14 @@ def topk_metrics(idx, held_out, n_items: int, Ks: Sequence[int] = (10, 20)) -> D
 
 
 def eval_topk(model, cfg, item_feats: torch.Tensor, edge_index: torch.Tensor,
-              train_pos_idx: Dict[int, np.ndarray], eval_pos: Dict[int, object], Ks=(10, 20), sampler=None):
+              train_pos_idx: Dict[int, np.ndarray], eval_pos: Dict[int, object], Ks=(10, 20), sampler=None,
+              edge_attr=None):
     """``eval_full``'s call shape with the metrics that need the lists: the model's forward, the
     max(Ks) best items outside each evaluated user's train history (``recommend_topk``), and
     ``topk_metrics`` against the held-out items.  ``eval_pos`` values: one item or a sequence of
     items per user.  ``cfg`` is unused."""
     with torch.no_grad():
-        Z = model(item_feats, edge_index)
+        Z = model(item_feats, edge_index, **_edge_kw(edge_attr))
     n_users, n_items = model.n_users, model.n_items
     if not eval_pos:
         return topk_metrics(np.zeros((0, max(Ks)), np.int64), [], n_items, Ks)
@@ -318,11 +326,11 @@ def eval_topk(model, cfg, item_feats: torch.Tensor, edge_index: torch.Tensor,
     return topk_metrics(idx, list(eval_pos.values()), n_items, Ks)
 
 
-def export_item_embeddings(model, item_feats: torch.Tensor, edge_index: torch.Tensor) -> np.ndarray:
+def export_item_embeddings(model, item_feats: torch.Tensor, edge_index: torch.Tensor, edge_attr=None) -> np.ndarray:
     """tools/export_item_embeddings.py:139-142: eval-mode no-grad forward, items' rows."""
     model.eval()
     with torch.no_grad():
-        Z = model(item_feats, edge_index)
+        Z = model(item_feats, edge_index, **_edge_kw(edge_attr))
         return Z[model.n_users:].detach().cpu().numpy().astype(np.float32)
 
 

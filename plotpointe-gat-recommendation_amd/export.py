@@ -30,7 +30,8 @@ def model_from_checkpoint(family: str, ckpt: dict, n_users: int, n_items: int, f
     if family == "gat_pyg":
         m = model_mod.PyGGAT(n_users, n_items, item_feat_dim=feat_dim, hidden=c.get("hidden_dim", 128),
                              layers=c.get("layers", 2), heads=c.get("heads", 1),
-                             attn_dropout=c.get("attn_dropout", 0.1))
+                             attn_dropout=c.get("attn_dropout", 0.1),
+                             edge_dim=1 if c.get("edge_features", "none") == "rating" else None)
     else:
         m = model_mod.CustomGAT(n_users, n_items, item_feat_dim=feat_dim, hidden=c.get("hidden_dim", 128),
                                 layers=c.get("layers", 2))
@@ -63,7 +64,10 @@ def main(argv=None):
     assert item_feats.shape[0] == n_items
     ckpt = torch.load(args.checkpoint, map_location=device, weights_only=True)
     m = model_from_checkpoint(args.model_family, ckpt, n_users, n_items, item_feats.size(1)).to(device)
-    I = evaluation.export_item_embeddings(m, item_feats, edge_index)
+    edge_attr = None
+    if ckpt.get("config", {}).get("edge_features", "none") == "rating":  # a model trained with --edge-features rating
+        edge_attr = torch.from_numpy(data.edge_attr_rating(tr, inter, u2i, i2i)).to(device)
+    I = evaluation.export_item_embeddings(m, item_feats, edge_index, edge_attr=edge_attr)
     Path(args.out_local).parent.mkdir(parents=True, exist_ok=True)
     np.save(args.out_local, I)
     print(f"[EXPORT] Wrote item embeddings: {args.out_local} shape={I.shape}")

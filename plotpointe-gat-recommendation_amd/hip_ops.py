@@ -121,6 +121,8 @@ class CSRGraph:
     # CSC position of each CSR slot (the inverse of csc2csr): pass B writes dz contiguously in
     # CSC order and the destination sums read it through this (_csr2csc builds it once)
     csr2csc: torch.Tensor = None
+    # staged edge attributes (stage_edge_attr): [(tensor ref, key, attr_csr, attr_csc)], newest last
+    edge_attr_staged: list = None
 
     @property
     def device(self):
@@ -222,6 +224,78 @@ graph_cache = _GraphCache()
 
 
 # ---------------------------------------------------------------------------
+# edge attributes (GATConv edge_dim): staging into slot order, once per (graph, tensor)
+# ---------------------------------------------------------------------------
+EDGE_MAX_DIM = 16  # include/ppgat.h PPGAT_EDGE_MAX_DIM
+# how many times stage_edge_attr permuted a tensor (a cache hit leaves it alone)
+EDGE_STAGE_COUNT = 0
+
+
+def check_edge_attr(edge_attr, n_edges: int, device) -> torch.Tensor:
+    """The user's ``edge_attr`` as [E, D] (1-D means D = 1, as in PyG): fp32, on ``device``, E rows,
+    1 <= D <= EDGE_MAX_DIM, no gradient -- edge features are inputs here."""
+    if not isinstance(edge_attr, torch.Tensor):
+        raise ValueError("edge_attr: expected a tensor")
+    if edge_attr.dtype != torch.float32:
+        raise ValueError(f"edge_attr: expected torch.float32, got {edge_attr.dtype}")
+    if edge_attr.device != device:
+        raise ValueError(f"edge_attr: on {edge_attr.device}, expected {device}")
+    if edge_attr.dim() not in (1, 2) or edge_attr.size(0) != n_edges:
+        raise ValueError(f"edge_attr: expected [{n_edges}] or [{n_edges}, D], got {tuple(edge_attr.shape)}")
+    if edge_attr.requires_grad:
+        raise NotImplementedError("edge_attr.requires_grad: gradients with respect to edge features are not "
+                                  "implemented")
+    D = 1 if edge_attr.dim() == 1 else edge_attr.size(1)
+    if D < 1:
+        raise ValueError("edge_attr: expected at least one feature per edge")
+    if D > EDGE_MAX_DIM:
+        raise NotImplementedError(f"edge_attr with {D} features per edge not implemented (edge_dim <= "
+                                  f"{EDGE_MAX_DIM})")
+    return edge_attr
+
+
+def stage_edge_attr(g: CSRGraph, edge_attr: torch.Tensor):
+    """(attr_csr, attr_csc) [E, D]: ``edge_attr`` in the CSR and CSC slot order of ``g``
+    (ppgat_edge_attr_permute), cached on the graph per (tensor object, version, pointers, shape) as
+    _const_colmax does -- never on an address alone.  A miss launches kernels and must not happen
+    inside a stream capture: stage eagerly first (a warm-up step, or this call)."""
+    global EDGE_STAGE_COUNT
+    edge_attr = check_edge_attr(edge_attr, g.n_edges, g.device)
+    key = (edge_attr._version, edge_attr.data_ptr(), edge_attr.untyped_storage().data_ptr(), tuple(edge_attr.shape),
+           tuple(edge_attr.stride()))
+    if g.edge_attr_staged is None:
+        g.edge_attr_staged = []
+    g.edge_attr_staged = [e for e in g.edge_attr_staged if e[0]() is not None]
+    for ref, k, a_csr, a_csc in g.edge_attr_staged:
+        if ref() is edge_attr and k == key:
+            return a_csr, a_csc
+    _require(not torch.cuda.is_current_stream_capturing(),
+             "stage_edge_attr: edge_attr is staged outside graph capture (run one eager step first)")
+    E = g.n_edges
+    D = 1 if edge_attr.dim() == 1 else edge_attr.size(1)
+    src = edge_attr.reshape(E, D).contiguous()
+    a_csr = torch.empty(max(E, 1), D, dtype=torch.float32, device=g.device)[:E]
+    a_csc = torch.empty(max(E, 1), D, dtype=torch.float32, device=g.device)[:E]
+    with torch.cuda.device(g.device):
+        _launch.edge_attr_permute(src, g.csr_eid, E, a_csr)
+        _launch.edge_attr_permute(src, g.csc_eid, E, a_csc)
+    EDGE_STAGE_COUNT += 1
+    g.edge_attr_staged = [e for e in g.edge_attr_staged if e[0]() is not edge_attr][-3:]
+    g.edge_attr_staged.append((weakref.ref(edge_attr), key, a_csr, a_csc))
+    return a_csr, a_csc
+
+
+def edge_terms(g: CSRGraph, staged, edge_v: torch.Tensor, heads: int, want_csc: bool):
+    """t_csr (and t_csc for the backward) [E, H] = staged attributes . edge_v [H, D] (ppgat_edge_terms)."""
+    a_csr, a_csc = staged
+    E = g.n_edges
+    t_csr = torch.empty(max(E, 1) * heads, dtype=torch.float32, device=edge_v.device)
+    t_csc = torch.empty(max(E, 1) * heads, dtype=torch.float32, device=edge_v.device) if want_csc else None
+    _launch.edge_terms(a_csr, a_csc if want_csc else None, edge_v, E, heads, t_csr, t_csc)
+    return t_csr, t_csc
+
+
+# ---------------------------------------------------------------------------
 # node scores / fused forward / fused backward
 # ---------------------------------------------------------------------------
 def node_scores(h: torch.Tensor, att_src: torch.Tensor, att_dst: torch.Tensor, heads: int, channels: int):
@@ -275,13 +349,13 @@ def seed_buffer(dropout_p: float, device) -> Optional[torch.Tensor]:
 
 
 def gat_fwd(g: CSRGraph, h, s_src, s_dst, bias, heads: int, channels: int, mode: int, slope: float,
-            dropout_p: float, seed: int, want_agg: bool, seed_buf: Optional[torch.Tensor] = None):
+            dropout_p: float, seed: int, want_agg: bool, seed_buf: Optional[torch.Tensor] = None, edge_term=None):
     N = g.n_nodes
     dev = h.device
     _require(h.size(0) == N, f"x has {h.size(0)} rows but the graph has {N} nodes")
     out, m, inv_l, agg = _fwd_outputs(N, heads, channels, want_agg, dev)
     _fwd_rows(g, g.fwd_sched, 0, N, h, s_src, s_dst, bias, heads, channels, mode, slope, dropout_p, seed, seed_buf,
-              out, m, inv_l, agg)
+              out, m, inv_l, agg, edge_term)
     return out, m, inv_l, agg
 
 
@@ -294,11 +368,11 @@ def _fwd_outputs(N: int, heads: int, channels: int, want_agg: bool, dev):
 
 
 def _fwd_rows(g: CSRGraph, sched: Schedule, r0: int, n: int, h, s_src, s_dst, bias, heads: int, channels: int,
-              mode: int, slope: float, dropout_p: float, seed: int, seed_buf, out, m, inv_l, agg):
+              mode: int, slope: float, dropout_p: float, seed: int, seed_buf, out, m, inv_l, agg, edge_term=None):
     """The forward over the destination rows [r0, r0 + n) of ``sched`` (row ids relative to
     r0; edge slots and source rows absolute): destination-indexed pointers are offset by r0."""
     _launch.fwd(sched, g.col, g.csr_eid, g.n_edges, r0, n, h, s_src, s_dst, bias, heads, channels, mode, slope,
-                dropout_p, seed, seed_buf, out, m, inv_l, agg)
+                dropout_p, seed, seed_buf, out, m, inv_l, agg, edge_term)
 
 
 def gat_bwd(g: CSRGraph, h, s_src, s_dst, att_src, att_dst, bias, out, agg, m, inv_l, grad_out, heads: int,
@@ -444,12 +518,12 @@ def gatv2_aggregate(xl, xr, att, bias, graph, heads, channels, slope, dropout_p=
 
 
 def _bwd_edges_src(g: CSRGraph, sched: Schedule, r0: int, h, s_src, nstate, grad_out, D, S, dz, heads, channels,
-                   mode, slope, p, seed, seed_buf=None):
+                   mode, slope, p, seed, seed_buf=None, edge_term=None):
     """Pass B over the source rows of ``sched`` (row ids relative to r0; edge slots and
     destination rows absolute) into D, S[:, :H] and dz -- dz in CSC order (dz_slot NULL: one
     contiguous store per edge instead of a 4-B scatter to its CSR slot)."""
     _launch.bwd_edges(sched, g.row, g.csc_eid, None, g.n_edges, r0, h, s_src, nstate, grad_out, heads, channels, mode,
-                      slope, p, seed, seed_buf, D, S, dz)
+                      slope, p, seed, seed_buf, D, S, dz, edge_term)
 
 
 def _bwd_dst_sum(g: CSRGraph, dz, S, heads):
@@ -458,14 +532,15 @@ def _bwd_dst_sum(g: CSRGraph, dz, S, heads):
 
 
 def _bwd_edges_dst(g: CSRGraph, h, s_src, nstate, grad_out, D, S, heads, channels, mode, slope, p, seed,
-                   seed_buf=None):
+                   seed_buf=None, edge_term=None):
     """Pass B into D [N, HC] (dh_msg) and S[:, :H] (ds_src); the destination sum into
     S[:, H:2H] (ds_dst).  S [N, 2H] is compact (its scattered per-node writes stay in L2)
-    and D keeps whole 512-B rows for the GEMMs that read it."""
+    and D keeps whole 512-B rows for the GEMMs that read it.  Returns dz [E, H] (CSC order)."""
     dz = torch.empty(max(g.n_edges, 1) * heads, dtype=torch.float32, device=h.device)
     _bwd_edges_src(g, g.bwd_sched, 0, h, s_src, nstate, grad_out, D, S, dz, heads, channels, mode, slope, p, seed,
-                   seed_buf)
+                   seed_buf, edge_term)
     _bwd_dst_sum(g, dz, S, heads)
+    return dz
 
 
 def project_supported(k: int, out_cols: int) -> bool:
@@ -624,7 +699,7 @@ class GATLayer(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, att_src, att_dst, bias, graph: CSRGraph, heads: int, channels: int, mode: int,
-                slope: float, dropout_p: float, seed: int, x_items=None, rep=None):
+                slope: float, dropout_p: float, seed: int, x_items=None, rep=None, edge_v=None, edge_staged=None):
         x_arg = x
         x = x.contiguous()
         x_items = x_items.contiguous() if x_items is not None else None
@@ -645,8 +720,17 @@ class GATLayer(torch.autograd.Function):
                 x_items = None
             h = mm_nn(x, W, 1, heads * channels)  # ppgat_gemm_nn (zero-padded where the shape needs it)
             s_src, s_dst = node_scores(h, a_s, a_d, heads, channels)
-        _tap_kinks(graph.rowptr, graph.col, graph.csr_eid, s_src, s_dst, heads)
         need = any(ctx.needs_input_grad[:5]) or (had_items and ctx.needs_input_grad[12])
+        t_csr = t_csc = None
+        if edge_v is not None:
+            # edge features: the per-slot logit terms of this step, in both slot orders when a backward follows
+            # a no-grad forward (eval, export) allocates nothing for a backward: needs_input_grad
+            # does not know about the grad mode, so gat_layer passes it along
+            need = (need or ctx.needs_input_grad[14]) and edge_staged[2]
+            ev = edge_v.detach().reshape(heads, -1).contiguous()
+            t_csr, t_csc = edge_terms(graph, edge_staged[:2], ev, heads, want_csc=need)
+        else:
+            _tap_kinks(graph.rowptr, graph.col, graph.csr_eid, s_src, s_dst, heads)
         ctx.seed_buf = seed_buffer(dropout_p, x.device) if need else None
         want_agg = (need or rep is not None) and heads > 1
         if rep is not None and graph.fwd_split is not None and rep.async_capable():
@@ -663,13 +747,15 @@ class GATLayer(torch.autograd.Function):
             rep.wait(pending)
         else:
             out, m, inv_l, agg = gat_fwd(graph, h, s_src, s_dst, b, heads, channels, mode, slope, dropout_p, seed,
-                                         want_agg=want_agg, seed_buf=ctx.seed_buf)
+                                         want_agg=want_agg, seed_buf=ctx.seed_buf, edge_term=t_csr)
             if rep is not None:  # replicated item rows (dist.py): merge their softmax over the ranks
                 rep.merge_fwd(out, m, inv_l, agg, b, heads, channels)
         if need:
             empty = torch.empty(0, device=x.device)
             ctx.save_for_backward(x, x_items if x_items is not None else empty, W, h, a_s, a_d, s_src, s_dst, out, m,
-                                  inv_l, agg if agg is not None else empty, b if b is not None else empty)
+                                  inv_l, agg if agg is not None else empty, b if b is not None else empty,
+                                  t_csc if t_csc is not None else empty)
+        ctx.edge = (edge_staged[1], tuple(edge_v.shape)) if edge_v is not None else None
         ctx.graph = graph
         ctx.rep = rep
         ctx.params = (weight, att_src, att_dst)
@@ -687,9 +773,10 @@ class GATLayer(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_out):
-        x, xi, W, h, a_s, a_d, s_src, s_dst, out, m, inv_l, agg, b = ctx.saved_tensors
+        x, xi, W, h, a_s, a_d, s_src, s_dst, out, m, inv_l, agg, b, t_csc = ctx.saved_tensors
         heads, C, mode, slope, p, seed, has_bias, has_agg, fused, seg, had_items, split = ctx.meta
         g = ctx.graph
+        et = t_csc if ctx.edge is not None else None
         lib = _lib.load()
         dev = x.device
         g_arg = g_out
@@ -726,10 +813,10 @@ class GATLayer(torch.autograd.Function):
             # the consumer layer's dx kernel already did this prologue (ppgat_project_bwd_fused_producer)
             nstate = pre[2]
             dbias = pre[3] if want_db else None
-            _bwd_edges_dst(g, h, s_src, nstate, g_out, D, S, heads, C, mode, slope, p, seed, ctx.seed_buf)
+            dz = _bwd_edges_dst(g, h, s_src, nstate, g_out, D, S, heads, C, mode, slope, p, seed, ctx.seed_buf, et)
         elif rep is None:
             prologue(0, N, dbias)
-            _bwd_edges_dst(g, h, s_src, nstate, g_out, D, S, heads, C, mode, slope, p, seed, ctx.seed_buf)
+            dz = _bwd_edges_dst(g, h, s_src, nstate, g_out, D, S, heads, C, mode, slope, p, seed, ctx.seed_buf, et)
         else:  # the replicated item rows enter dbias on one rank only
             RU = rep.RU
             db_i = torch.empty(C, dtype=torch.float32, device=dev) if (want_db and rep.rank == 0) else None
@@ -749,6 +836,14 @@ class GATLayer(torch.autograd.Function):
                 _bwd_edges_dst(g, h, s_src, nstate, g_out, D, S, heads, C, mode, slope, p, seed, ctx.seed_buf)
             if db_i is not None:
                 dbias = dbias + db_i
+        dv = None
+        if ctx.edge is not None and ctx.needs_input_grad[14]:
+            # dv[h, d] = sum_k dz[k, h] attr_csc[k, d]: the caller's autograd turns it into
+            # the lin_edge.weight and att_edge gradients
+            attr_csc, v_shape = ctx.edge
+            dv = torch.empty(heads, attr_csc.size(1), dtype=torch.float32, device=dev)
+            _launch.edge_dv(dz, attr_csc, g.n_edges, heads, attr_csc.size(1), dv)
+            dv = dv.view(v_shape)
         need_dx = ctx.needs_input_grad[0] or (had_items and ctx.needs_input_grad[12])
         dx = None
         if (heads == 1 and HC == K and bool(lib.ppgat_project_bwd_fused_supported(K)) and _fused_dxw_enabled()
@@ -783,7 +878,7 @@ class GATLayer(torch.autograd.Function):
             dx_u = dx[:split] if (dx is not None and had_items) else dx
             dx_i = dx[split:] if (dx is not None and had_items) else None
             return (dx_u, dW, datt_src.view(ctx.att_shapes[0]), datt_dst.view(ctx.att_shapes[1]), dbias,
-                    None, None, None, None, None, None, None, dx_i, None)
+                    None, None, None, None, None, None, None, dx_i, None, dv, None)
         if need_dx:
             if heads == 1 and project_supported(HC, K):  # reduction over HC, K output columns
                 dx = torch.empty(N, K, dtype=torch.float32, device=dev)
@@ -809,19 +904,36 @@ class GATLayer(torch.autograd.Function):
         dx_u = dx[:split] if (dx is not None and had_items) else dx
         dx_i = dx[split:] if (dx is not None and had_items) else None
         return (dx_u, dW, datt_src.view(ctx.att_shapes[0]), datt_dst.view(ctx.att_shapes[1]), dbias,
-                None, None, None, None, None, None, None, dx_i, None)
+                None, None, None, None, None, None, None, dx_i, None, dv, None)
 
 
 def gat_layer(x, weight, att_src, att_dst, bias, graph, heads, channels, mode, slope, dropout_p=0.0, seed=0,
-              x_items=None, rep=None):
+              x_items=None, rep=None, edge_v=None, edge_attr=None):
     """x [N, F] -> out [N, C]: lin + the fused GAT aggregation, with the fused backward.
-    With ``x_items``, the input rows are cat(x, x_items) (never materialised on the fused path)."""
+    With ``x_items``, the input rows are cat(x, x_items) (never materialised on the fused path).
+    With ``edge_v`` [H, D] (differentiable) and ``edge_attr`` [E, D] (an input; staged once per
+    graph, stage_edge_attr), the logit of edge k gains <edge_attr[k], edge_v[h]> -- GATConv's
+    edge_dim term with lin_edge and att_edge collapsed to edge_v; transform-then-aggregate only."""
     _require(x.is_cuda, "gat_layer: ppgat runs on ROCm devices only; there is no CPU path")
     if x.dtype != torch.float32 or x.dim() != 2:
         raise NotImplementedError("ppgat gat_layer: fp32 2-D input only")
     if x_items is not None:
         _require(x_items.is_cuda and x_items.dtype == torch.float32 and x_items.dim() == 2
                  and x_items.size(1) == x.size(1), "gat_layer: x_items must match x in dtype/device/width")
+    if (edge_v is None) != (edge_attr is None):
+        raise ValueError("gat_layer: edge_v and edge_attr go together")
+    if edge_v is not None:
+        if rep is not None:
+            raise NotImplementedError("gat_layer: edge features on the replicated (sharded) layer are not implemented")
+        if mode != _lib.MODE_PYG:
+            raise NotImplementedError("gat_layer: edge features are GATConv's (PyG mode) only")
+        staged = stage_edge_attr(graph, edge_attr)
+        D = staged[0].size(1)
+        if not (isinstance(edge_v, torch.Tensor) and edge_v.dtype == torch.float32 and edge_v.device == x.device
+                and edge_v.numel() == heads * D):
+            raise ValueError(f"edge_v: expected an fp32 [{heads}, {D}] tensor on {x.device}")
+        return GATLayer.apply(x, weight, att_src, att_dst, bias, graph, heads, channels, mode, slope, dropout_p, seed,
+                              x_items, None, edge_v, staged + (torch.is_grad_enabled(),))
     if (mode == _lib.MODE_PYG and heads > 1 and heads * channels > x.size(1) and rep is None
             and xgat_supported(x.size(1), heads, channels)):
         # multi-head layers wider than their input: aggregate x, then transform (config 5)
@@ -1595,7 +1707,10 @@ class GATLayerX(torch.autograd.Function):
 
 
 def gat_layer_x(x, weight, att_src, att_dst, bias, views: XViews, heads: int, channels: int, slope: float,
-                dropout_p: float = 0.0, seed: int = 0):
+                dropout_p: float = 0.0, seed: int = 0, edge_v=None, edge_attr=None):
+    if edge_v is not None or edge_attr is not None:
+        raise NotImplementedError("gat_layer_x: edge features on the aggregate-then-transform layer are not "
+                                  "implemented")
     _require(x.is_cuda, "gat_layer_x: ppgat runs on ROCm devices only; there is no CPU path")
     return GATLayerX.apply(x, weight, att_src, att_dst, bias, views, heads, channels, float(slope), float(dropout_p),
                            int(seed))

@@ -70,7 +70,9 @@ def _unalias_state(module, state_dict, prefix, local_metadata):
         state_dict[k] = v.clone()
 
 
-def _stack(model, item_proj, item_feats, layers, edge_index):
+def _stack(model, item_proj, item_feats, layers, edge_index, edge_attr=None):
+    """``edge_attr`` (GATConv layers built with edge_dim): the same tensor feeds every layer."""
+    ea = {} if edge_attr is None else {"edge_attr": edge_attr}
     user_w = model.user_emb.weight
     if user_w.is_cuda and os.environ.get("PPGAT_NODE_TABLE", "1") != "0":
         table = node_table(model, item_feats.size(0))
@@ -83,24 +85,25 @@ def _stack(model, item_proj, item_feats, layers, edge_index):
         v = hip_ops.linear(item_feats, item_proj.weight, item_proj.bias)
     if len(layers) == 0:
         return torch.cat([user_w, v], dim=0)
-    x = layers[0].forward_segments(user_w, v, edge_index)
+    x = layers[0].forward_segments(user_w, v, edge_index, **ea)
     for layer in list(layers)[1:]:
-        x = layer(x, edge_index)
+        x = layer(x, edge_index, **ea)
     return x
 
 
 class PyGGAT(torch.nn.Module):
     def __init__(self, n_users: int, n_items: int, item_feat_dim: int, hidden: int, layers: int, heads: int,
-                 attn_dropout: float):
+                 attn_dropout: float, edge_dim=None):
         super().__init__()
         self.n_users, self.n_items = n_users, n_items
+        self.edge_dim = edge_dim
         self.user_emb = torch.nn.Embedding(n_users, hidden)
         torch.nn.init.normal_(self.user_emb.weight, std=0.1)
         self.item_proj = torch.nn.Linear(item_feat_dim, hidden)
         self.convs = torch.nn.ModuleList()
         for _ in range(layers):
             self.convs.append(GATConv(hidden, hidden, heads=heads, dropout=attn_dropout, add_self_loops=False,
-                                      concat=False))
+                                      concat=False, edge_dim=edge_dim))
         self._register_state_dict_hook(_unalias_state)
 
     def node_features(self, item_feats: torch.Tensor) -> torch.Tensor:
@@ -108,8 +111,8 @@ class PyGGAT(torch.nn.Module):
         v = hip_ops.linear(item_feats, self.item_proj.weight, self.item_proj.bias)
         return torch.cat([u, v], dim=0)
 
-    def forward(self, item_feats: torch.Tensor, edge_index: torch.Tensor) -> torch.Tensor:
-        return _stack(self, self.item_proj, item_feats, self.convs, edge_index)
+    def forward(self, item_feats: torch.Tensor, edge_index: torch.Tensor, edge_attr=None) -> torch.Tensor:
+        return _stack(self, self.item_proj, item_feats, self.convs, edge_index, edge_attr)
 
 
 class PyGGATv2(torch.nn.Module):

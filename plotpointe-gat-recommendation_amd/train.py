@@ -98,6 +98,7 @@ class Config:
     loss: str = "bpr"
     model_family: str = "gat_pyg"
     share_weights: bool = False  # gatv2_pyg: lin_r is lin_l
+    edge_features: str = "none"  # gat_pyg: "rating" feeds (r - 1) / 4 per edge to GATConv(edge_dim=1)
 
 
 @dataclass
@@ -152,10 +153,43 @@ def load_inputs(cfg: Config, synthetic: Optional[str]):
     return tr, va, te, int(maps["n_users"]), int(maps["n_items"]), feats
 
 
+def load_edge_attr(cfg: Config, synthetic: Optional[str], tr) -> Optional[np.ndarray]:
+    """The edge features of ``data.build_edge_index(n_users, n_items, tr)`` under cfg.edge_features:
+    None, or the rating weights [E, 1] (data.edge_attr_rating) from the interactions load_inputs
+    read (config 2's synthetic graph has no ratings: 1.0 per edge)."""
+    if getattr(cfg, "edge_features", "none") == "none":
+        return None
+    if synthetic == "cfg2":
+        return data.edge_attr_rating(tr)
+    if synthetic:
+        inter = data.synthetic_interactions_small(seed=0)
+        maps = data.node_maps_from_interactions(inter)
+    else:
+        import pandas as pd
+        inter = pd.read_parquet(_local(cfg.staging_prefix) / "interactions.parquet")
+        with open(_local(cfg.graphs_prefix) / "node_maps.json") as f:
+            maps = json.load(f)
+    u2i, i2i = data.index_maps(maps)
+    return data.edge_attr_rating(tr, inter, u2i, i2i)
+
+
+def check_edge_features(args):
+    """--edge-features other than none: --model-family gat_pyg on one GPU only."""
+    if args.edge_features == "none":
+        return
+    if args.model_family != "gat_pyg":
+        raise NotImplementedError(f"--edge-features {args.edge_features} with --model-family {args.model_family} is "
+                                  "not implemented: edge features are GATConv's (--model-family gat_pyg)")
+    if args.world_size > 1:
+        raise NotImplementedError(f"--edge-features {args.edge_features} with --world-size {args.world_size} is not "
+                                  "implemented: the sharded layers take no edge features (--world-size 1)")
+
+
 def build_model(cfg: Config, n_users: int, n_items: int, feat_dim: int):
     if cfg.model_family == "gat_pyg":
         return model_mod.PyGGAT(n_users, n_items, item_feat_dim=feat_dim, hidden=cfg.hidden_dim, layers=cfg.layers,
-                                heads=cfg.heads, attn_dropout=cfg.attn_dropout)
+                                heads=cfg.heads, attn_dropout=cfg.attn_dropout,
+                                edge_dim=1 if getattr(cfg, "edge_features", "none") == "rating" else None)
     if cfg.model_family == "gatv2_pyg":
         return model_mod.PyGGATv2(n_users, n_items, item_feat_dim=feat_dim, hidden=cfg.hidden_dim, layers=cfg.layers,
                                   heads=cfg.heads, attn_dropout=cfg.attn_dropout, share_weights=cfg.share_weights)
@@ -165,7 +199,7 @@ def build_model(cfg: Config, n_users: int, n_items: int, feat_dim: int):
     return m
 
 
-def epoch_step(model, opt, item_feats, edge_index, n_users: int, u, i, j, loss: str = "bpr"):
+def epoch_step(model, opt, item_feats, edge_index, n_users: int, u, i, j, loss: str = "bpr", edge_attr=None):
     """One epoch's optimisation step on one GPU (train_gat_custom.py:349-362, identical
     train_gat_pyg.py:307-323): the training forward over the whole graph, the BPR/BCE loss of
     the epoch's sampled triples, zero_grad, backward, ``opt.step()``.  Returns the loss.
@@ -176,7 +210,7 @@ def epoch_step(model, opt, item_feats, edge_index, n_users: int, u, i, j, loss: 
     if os.environ.get("PPGAT_BPR_OVERLAP", "0") == "1":
         C = model.user_emb.weight.size(1)
         prep = model_mod.hip_ops.bpr_prepare(n_users + model.n_items, n_users, model.n_items, C, u, i, j)
-    Z = model(item_feats, edge_index)
+    Z = model(item_feats, edge_index) if edge_attr is None else model(item_feats, edge_index, edge_attr)
     lo = model_mod.bpr_loss(Z, n_users, u, i, j, loss, prepared=prep)
     opt.zero_grad()
     lo.backward()
@@ -197,12 +231,13 @@ FULL_EVAL_NOTE = ("Evaluation ranks the held-out positive against every item out
                   "(full ranking, no sampled negatives).")
 
 
-def evaluate(args, model, cfg, item_feats, edge_index, tr, eval_pos, dev_sampler, seed):
+def evaluate(args, model, cfg, item_feats, edge_index, tr, eval_pos, dev_sampler, seed, edge_attr=None):
     """One evaluation under --eval-mode: the reference's sampled protocol, or the full ranking."""
     if args.eval_mode == "full":
-        return evaluation.eval_full(model, cfg, item_feats, edge_index, tr, eval_pos, sampler=dev_sampler)
+        return evaluation.eval_full(model, cfg, item_feats, edge_index, tr, eval_pos, sampler=dev_sampler,
+                                    edge_attr=edge_attr)
     return evaluation.eval_sampled(model, cfg, item_feats, edge_index, tr, eval_pos, fast=args.fast_eval,
-                                   sampler=dev_sampler if args.device_eval else None, seed=seed)
+                                   sampler=dev_sampler if args.device_eval else None, seed=seed, edge_attr=edge_attr)
 
 
 def raw_id_maps(cfg: Config, synthetic: Optional[str], n_users: int, n_items: int):
@@ -225,7 +260,7 @@ def raw_id_maps(cfg: Config, synthetic: Optional[str], n_users: int, n_items: in
 
 
 def write_recommendations(args, cfg: Config, model, item_feats, edge_index, tr, n_users: int, n_items: int,
-                          dev_sampler, device):
+                          dev_sampler, device, edge_attr=None):
     """--recommend-out: the --recommend-k best items outside each user's train history for EVERY
     user (evaluation.recommend_topk on the model's final embeddings), written as an .npz with
     ``users`` [n_users], ``items`` [n_users, K] (-1 = fewer than K eligible), ``scores`` and the
@@ -234,7 +269,7 @@ def write_recommendations(args, cfg: Config, model, item_feats, edge_index, tr, 
         ptr, flat = user_csr(tr, n_users)
         dev_sampler = sampler_mod.BPRSampler(ptr, flat, n_items, device=device)
     with torch.no_grad():
-        Z = model(item_feats, edge_index)
+        Z = model(item_feats, edge_index) if edge_attr is None else model(item_feats, edge_index, edge_attr)
     k = int(args.recommend_k)
     idx, sc = evaluation.recommend_topk(Z[:n_users], Z[n_users:n_users + n_items], None, k=k, sampler=dev_sampler)
     idx, sc = idx.cpu().numpy(), sc.cpu().numpy()
@@ -373,6 +408,9 @@ def build_parser():
     ap.add_argument("--model-family", choices=["gat_pyg", "gat_custom", "lightgcn", "gatv2_pyg"], default="gat_pyg",
                     help="gatv2_pyg: PyGGAT with GATv2Conv layers (dynamic attention), one GPU")
     ap.add_argument("--share-weights", action="store_true", help="gatv2_pyg: GATv2Conv(share_weights=True)")
+    ap.add_argument("--edge-features", choices=["none", "rating"], default="none",
+                    help="gat_pyg on one GPU: rating feeds (r - 1) / 4 of each train interaction to "
+                         "GATConv(edge_dim=1) as its edge feature")
     ap.add_argument("--hidden-dim", type=int, default=128)
     ap.add_argument("--layers", type=int, default=None, help="default 2 (GAT), 3 (lightgcn)")
     ap.add_argument("--heads", type=int, default=1)
@@ -417,6 +455,7 @@ def build_parser():
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    check_edge_features(args)
     if args.recommend_out and args.world_size > 1:
         raise NotImplementedError("--recommend-out runs on one GPU (--world-size 1): the lists are made from the "
                                   "whole user and item tables")
@@ -434,7 +473,8 @@ def main(argv=None):
                  models_prefix=args.models_prefix, hidden_dim=args.hidden_dim, layers=args.layers, heads=args.heads,
                  attn_dropout=args.attn_dropout, epochs=args.epochs, samples_per_epoch=args.samples_per_epoch,
                  seed=args.seed, eval_neg_k=args.eval_neg_k, item_features=args.item_features, loss=args.loss,
-                 model_family=args.model_family, share_weights=args.share_weights)
+                 model_family=args.model_family, share_weights=args.share_weights,
+                 edge_features=args.edge_features)
     if args.lr is not None:
         cfg.lr = args.lr
     if args.l2 is not None:
@@ -465,6 +505,8 @@ def main(argv=None):
     edge_index = data.build_edge_index(n_users, n_items, tr).to(device)
     item_feats = torch.tensor(feats_np, dtype=torch.float32).to(device)
     assert item_feats.shape[0] == n_items
+    ea_np = load_edge_attr(cfg, args.synthetic, tr)
+    edge_attr = torch.from_numpy(ea_np).to(device) if ea_np is not None else None  # one tensor for the whole run
     model = build_model(cfg, n_users, n_items, item_feats.size(1)).to(device)
     sharded = None
     if world > 1:
@@ -509,7 +551,8 @@ def main(argv=None):
             i = torch.from_numpy(i_arr).long().to(device)
             j = torch.from_numpy(j_arr).long().to(device)
         if sharded is None:
-            loss_val = float(epoch_step(model, opt, item_feats, edge_index, n_users, u, i, j, cfg.loss).item())
+            loss_val = float(epoch_step(model, opt, item_feats, edge_index, n_users, u, i, j, cfg.loss,
+                                        edge_attr=edge_attr).item())
         else:
             # each rank: its own users' triples (the sum over ranks is the reference's mean),
             # dense gradients all-reduced, user rows updated by their owner
@@ -527,7 +570,8 @@ def main(argv=None):
         if lead:
             print(f"[{tag}][Epoch {epoch}] loss={loss_val:.4f} ({cfg.loss})")
         eval_model.eval()
-        val_metrics = evaluate(args, eval_model, cfg, item_feats, edge_index, tr, va, dev_sampler, cfg.seed + epoch)
+        val_metrics = evaluate(args, eval_model, cfg, item_feats, edge_index, tr, va, dev_sampler, cfg.seed + epoch,
+                               edge_attr=edge_attr)
         if lead:
             print(f"[{tag}][Epoch {epoch}] val: {val_metrics}")
         if args.structured_logs and lead:
@@ -548,7 +592,8 @@ def main(argv=None):
             ids = torch.as_tensor(sharded.dg.own_user_ids(), dtype=torch.int64, device=model.user_emb.weight.device)
             sharded.user_emb_local.copy_(model.user_emb.weight.index_select(0, ids))
     eval_model.eval()
-    test_metrics = evaluate(args, eval_model, cfg, item_feats, edge_index, tr, te, dev_sampler, cfg.seed)
+    test_metrics = evaluate(args, eval_model, cfg, item_feats, edge_index, tr, te, dev_sampler, cfg.seed,
+                            edge_attr=edge_attr)
     if lead:
         print(f"[{tag}] test: {test_metrics}")
     out = {"best_val_ndcg@20": float(best), "val": val_metrics, "test": test_metrics, "config": cfg.__dict__,
@@ -559,7 +604,7 @@ def main(argv=None):
         out["notes"] += "; " + FULL_EVAL_NOTE
     if args.recommend_out:  # one GPU (refused above otherwise)
         out["recommendations"] = write_recommendations(args, cfg, model, item_feats, edge_index, tr, n_users, n_items,
-                                                       dev_sampler, device)
+                                                       dev_sampler, device, edge_attr=edge_attr)
     if world > 1:
         import torch.distributed as tdist
         tdist.destroy_process_group()
