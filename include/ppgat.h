@@ -438,7 +438,12 @@ int ppgat_dropout_set_epoch(uint64_t epoch, void* stream);
  * all n_cols items (row stride ld floats).  Writes, per row, the k best (item, similarity)
  * sorted by similarity descending with ties by smaller item index (out_idx / out_sim
  * [rows, k]; -1 / -inf where fewer than k items exist) and out_cnt[row] = how many of them
- * reach min_sim (a prefix).  k <= ppgat_knn_max_k().  Deterministic. */
+ * reach min_sim, sim >= min_sim (a prefix).  An entry of S that is -inf or NaN is absent, like
+ * the item itself (column q0 + row; q0 = n_cols means no column is the item): it is never
+ * selected, whatever k, and never counted.  The -1 / -inf pads are not items and are not
+ * counted either, so with min_sim = -inf out_cnt is the number of items written.  Columns n_cols .. ld - 1 are never read.
+ * Refused with nothing written: k outside [1, ppgat_knn_max_k()] (PPGAT_ERR_UNSUPPORTED),
+ * n_cols < 1, ld < n_cols, q0 < 0 (PPGAT_ERR_INVALID).  Deterministic. */
 int ppgat_knn_max_k(void);
 int ppgat_knn_topk(const float* S, int64_t ld, int64_t rows, int64_t n_cols, int64_t q0, int k, float min_sim,
                    int32_t* out_idx, float* out_sim, int32_t* out_cnt, void* stream);

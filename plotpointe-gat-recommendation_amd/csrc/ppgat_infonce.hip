@@ -1,7 +1,7 @@
 // ppgat_infonce.hip -- the FusionMLP training step's contrastive loss and its backward on the
 // device (embeddings/fuse_modal.py:39-72 contrastive_fusion_loss, trained by :179-214).
 //
-// Per batch of B rows (B <= 1024) with F = fused [B, D], T = txt_proj [B, D], I = img_proj [B, D]:
+// Per batch of B rows (1 <= B <= 4096, infonce_shape_ok) with F = fused [B, D], T = txt_proj [B, D], I = img_proj [B, D]:
 //   Fn = F / max(|F|, 1e-12)  (torch F.normalize), likewise Tn, In
 //   S_t = Fn Tn^T / tau,  S_i = Fn In^T / tau                      [B, B]
 //   loss_t = mean_b (logsumexp_c S_t[b, c] - S_t[b, b]),  loss_i likewise
@@ -119,11 +119,14 @@ __global__ void __launch_bounds__(256) k_ce_rows(float* __restrict__ S1, float* 
   float se = 0.f;
   for (int64_t c = threadIdx.x; c < B; c += 256) se += expf(S[c] - mx);
   se = block_sum(se, red);
-  const float lse = mx + logf(se);
+  // log softmax as (S - max) - log(sum): the first difference is exact near the maximum, where the
+  // probabilities that matter sit; forming lse = max + log(sum) first would round at the logits'
+  // magnitude (1 / tau) and put that error, ulp(1 / tau) / 2 relative, on every entry of the row
+  const float lg = logf(se);
   const float diag = S[b];
   __syncthreads();
-  for (int64_t c = threadIdx.x; c < B; c += 256) S[c] = (expf(S[c] - lse) - (c == b ? 1.f : 0.f)) * gscale;
-  if (threadIdx.x == 0) l[blockIdx.y * B + b] = lse - diag;
+  for (int64_t c = threadIdx.x; c < B; c += 256) S[c] = (expf((S[c] - mx) - lg) - (c == b ? 1.f : 0.f)) * gscale;
+  if (threadIdx.x == 0) l[blockIdx.y * B + b] = lg + (mx - diag);
 }
 
 // loss = (mean l_t + mean l_i) / 2 -> out[0] = loss, out[1] = loss_t, out[2] = loss_i

@@ -1,7 +1,9 @@
 // ppgat_knn.hip -- neighbour selection of the I-I kNN build (graphs/build_ii_knn.py:76-99),
 // after the cosine-similarity block S = E_q E^T (library GEMM, the only dense part):
 // per query row, the k largest similarities excluding the item itself, sorted descending
-// (ties: smaller item index first), and how many of them reach min_similarity.
+// (ties: smaller item index first), and how many of them reach min_similarity.  An entry of
+// -inf or NaN is absent: it never beats a lane's threshold (s > thr is false for both), so it
+// is never selected and never counted.
 //
 // One wave per row.  Each lane scans a strided slice of the row (coalesced 256-B loads,
 // 4 in flight) keeping its own sorted top-k list in LDS ([slot][lane] so the 64 lanes hit
@@ -79,7 +81,9 @@ __global__ void __launch_bounds__(256) k_knn_topk(const float* __restrict__ S, i
       out_sim[r * k + t] = bv;
       out_idx[r * k + t] = bi == INT32_MAX ? -1 : bi;
     }
-    cnt += bv >= min_sim ? 1 : 0;  // sorted descending: the kept entries are a prefix
+    // sorted descending: the kept entries are a prefix; a pad (-1 / -inf) is no item and is not
+    // counted even where min_sim = -inf
+    cnt += (bi != INT32_MAX && bv >= min_sim) ? 1 : 0;
   }
   if (lane == 0 && out_cnt != nullptr) out_cnt[r] = cnt;
 }
