@@ -295,6 +295,31 @@ int ppgat_bpr_bwd_producer(const float* Z, int64_t n_rows, int64_t n_users, int6
                            const float* prev_m, const float* prev_inv_l, float prev_gscale, float* prev_nstate,
                            float* prev_grad_bias, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- sampled-softmax loss: one positive against M sampled negatives -----------
+ * Replaces: nothing one-to-one -- the reference trains on one negative per positive
+ *           (scripts/train_gat_pyg.py:313-322).  In torch terms, with cand [S, M + 1] (column 0
+ *           the positive, e.g. from ppgat_eval_sample):
+ *             s = (Z[u][:, None, :] * Z[n_users + cand]).sum(-1) / temperature
+ *             loss = (s.logsumexp(1) - s[:, 0]).mean()
+ *           and its autograd (index_select backward = index_add_ with float atomics).
+ * Z [n_rows, C] with n_rows = n_users + n_items; u int64 [S]; cand int64 [S, n_cand], n_cand =
+ * M + 1 >= 2.  A candidate may repeat in a row and the positive may appear among the negatives:
+ * both simply add terms.  The forward writes the scalar mean loss and coef [S, n_cand] =
+ * (softmax - [m == 0]) / (S temperature); the backward writes every row of grad_Z [n_rows, C]
+ * exactly once (zero rows included) = grad_loss (a device scalar) times the sums of the
+ * contributions, without float atomics: sorted records, ordered sums, the same bits on every
+ * launch.  n_samples == 0: loss 0, zero gradient.  Indices outside their range are clamped and
+ * counted into bad_count (device int32[1], nullable; written by the call).  Both calls take the
+ * workspace of the first function (host only); the backward needs nothing the forward left in it.
+ */
+int ppgat_ssm_workspace_bytes(int64_t n_rows, int64_t n_samples, int64_t n_cand, int channels, size_t* bytes);
+int ppgat_ssm_fwd(const float* Z, int64_t n_rows, int64_t n_users, int64_t n_items, int channels, const int64_t* u,
+                  const int64_t* cand, int64_t n_samples, int64_t n_cand, float temperature, float* loss, float* coef,
+                  int32_t* bad_count, void* workspace, size_t workspace_bytes, void* stream);
+int ppgat_ssm_bwd(const float* Z, int64_t n_rows, int64_t n_users, int64_t n_items, int channels, const int64_t* u,
+                  const int64_t* cand, int64_t n_samples, int64_t n_cand, float temperature, const float* coef,
+                  const float* grad_loss, float* grad_Z, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- projection weight gradient ----------------------------------------------
  * Replaces: the weight (and bias) gradient of torch.nn.Linear in GATConv.lin /
  *           SimpleGATLayer.lin (train_gat_custom.py:66,77) and PyGGAT.item_proj

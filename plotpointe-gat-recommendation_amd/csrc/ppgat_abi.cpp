@@ -4,6 +4,7 @@
 // error strings, and optional per-kernel HIP-event timing on the launch stream.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <mutex>
 #include <string>
 #include <utility>
@@ -614,6 +615,62 @@ int ppgat_bpr_bwd_prepared(const float* Z, int64_t n_rows, int64_t n_users, int6
   hipError_t e = ppgat::bpr_bwd_finish(Z, n_rows, n_users, n_items, row_map, channels, u, i, j, n_samples, coef,
                                        grad_loss, grad_Z, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
   if (e != hipSuccess) return hip_fail(e, "bpr_bwd_prepared");
+  return PPGAT_OK;
+}
+
+// ---- sampled-softmax loss ----
+static int check_ssm(int64_t n_rows, int64_t n_users, int64_t n_items, int channels, int64_t S, int64_t n_cand,
+                     float temperature, const char* who) {
+  if (!ppgat::bpr_channels_ok(channels))
+    return fail(PPGAT_ERR_UNSUPPORTED, std::string(who) + ": channels must be 32/64/128/256");
+  if (n_cand < 2) return fail(PPGAT_ERR_INVALID, std::string(who) + ": n_cand must be >= 2 (the positive and a negative)");
+  if (!(temperature > 0.f) || !std::isfinite(temperature))
+    return fail(PPGAT_ERR_INVALID, std::string(who) + ": temperature must be finite and > 0");
+  if (n_users < 1 || n_items < 1 || S < 0 || n_rows != n_users + n_items)
+    return fail(PPGAT_ERR_INVALID, std::string(who) + ": bad sizes (n_rows must be n_users + n_items)");
+  if (n_rows >= ((int64_t)1 << 31) - 1 || n_cand >= ((int64_t)1 << 31) ||
+      (double)S * (double)(n_cand + 1) >= 2147483648.0)
+    return fail(PPGAT_ERR_INVALID, std::string(who) + ": n_samples * (n_cand + 1) and n_rows must be < 2^31");
+  return PPGAT_OK;
+}
+
+int ppgat_ssm_workspace_bytes(int64_t n_rows, int64_t n_samples, int64_t n_cand, int channels, size_t* bytes) {
+  if (!ppgat::bpr_channels_ok(channels))
+    return fail(PPGAT_ERR_UNSUPPORTED, "ssm_workspace_bytes: channels must be 32/64/128/256");
+  if (!bytes || n_rows < 0 || n_samples < 0 || n_cand < 2 || n_rows >= ((int64_t)1 << 31) - 1 ||
+      n_cand >= ((int64_t)1 << 31) || (double)n_samples * (double)(n_cand + 1) >= 2147483648.0)
+    return fail(PPGAT_ERR_INVALID, "ssm_workspace_bytes: bad arguments");
+  *bytes = ppgat::ssm_workspace_bytes(n_rows, n_samples, (int)n_cand, channels);
+  return PPGAT_OK;
+}
+
+int ppgat_ssm_fwd(const float* Z, int64_t n_rows, int64_t n_users, int64_t n_items, int channels, const int64_t* u,
+                  const int64_t* cand, int64_t n_samples, int64_t n_cand, float temperature, float* loss, float* coef,
+                  int32_t* bad_count, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = check_ssm(n_rows, n_users, n_items, channels, n_samples, n_cand, temperature, "ssm_fwd")) return rc;
+  if (!Z || !loss || (n_samples > 0 && (!u || !cand || !coef))) return fail(PPGAT_ERR_INVALID, "ssm_fwd: null pointer");
+  if (!workspace || workspace_bytes < ppgat::ssm_workspace_bytes(n_rows, n_samples, (int)n_cand, channels))
+    return fail(PPGAT_ERR_INVALID, "ssm_fwd: workspace too small");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = debug_range(u, 8, n_samples, 0, n_users, "ssm_fwd: u", st)) return rc;
+  if (int rc = debug_range(cand, 8, n_samples * n_cand, 0, n_items, "ssm_fwd: cand", st)) return rc;
+  hipError_t e = ppgat::ssm_fwd(Z, n_users, n_items, channels, u, cand, n_samples, (int)n_cand, temperature, loss, coef,
+                                bad_count, workspace, st);
+  if (e != hipSuccess) return hip_fail(e, "ssm_fwd");
+  return PPGAT_OK;
+}
+
+int ppgat_ssm_bwd(const float* Z, int64_t n_rows, int64_t n_users, int64_t n_items, int channels, const int64_t* u,
+                  const int64_t* cand, int64_t n_samples, int64_t n_cand, float temperature, const float* coef,
+                  const float* grad_loss, float* grad_Z, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = check_ssm(n_rows, n_users, n_items, channels, n_samples, n_cand, temperature, "ssm_bwd")) return rc;
+  if (!Z || !grad_Z || !grad_loss || (n_samples > 0 && (!u || !cand || !coef)))
+    return fail(PPGAT_ERR_INVALID, "ssm_bwd: null pointer");
+  if (!workspace || workspace_bytes < ppgat::ssm_workspace_bytes(n_rows, n_samples, (int)n_cand, channels))
+    return fail(PPGAT_ERR_INVALID, "ssm_bwd: workspace too small");
+  hipError_t e = ppgat::ssm_bwd(Z, n_users, n_items, channels, u, cand, n_samples, (int)n_cand, coef, grad_loss, grad_Z,
+                                workspace, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail(e, "ssm_bwd");
   return PPGAT_OK;
 }
 

@@ -87,6 +87,22 @@ hipError_t bpr_bwd_finish(const float* Z, int64_t n_rows, int64_t n_users, int64
                           int C, const int64_t* u, const int64_t* i, const int64_t* j, int64_t S, const float* coef,
                           const float* grad_loss, float* dZ, void* ws, size_t ws_bytes, hipStream_t st,
                           const BprProducer* prod = nullptr);
+// the stable LSD radix sort of (key, value) int32 pairs of the loss backwards (keys < 2^bits):
+// sorts (k0, v0) with (k1, v1) as the ping-pong pair, *result_in_1 says where the result ended
+// (after an odd number of passes: ceil(bits / 10)); mark != NULL: the last pass also sets
+// mark[k] = 1 for every key k < mark_n.  ws: rs_workspace_bytes(n, bits).
+size_t rs_workspace_bytes(int64_t n, unsigned bits);
+hipError_t rs_sort(int32_t* k0, int32_t* v0, int32_t* k1, int32_t* v1, int64_t n, unsigned bits, void* ws,
+                   bool* result_in_1, hipStream_t st, uint8_t* mark = nullptr, int64_t mark_n = 0);
+
+// sampled-softmax loss (ppgat_ssm.hip): cand [S, K1], column 0 the positive; n_rows = n_users + n_items
+size_t ssm_workspace_bytes(int64_t N, int64_t S, int K1, int C);
+hipError_t ssm_fwd(const float* Z, int64_t n_users, int64_t n_items, int C, const int64_t* u, const int64_t* cand,
+                   int64_t S, int K1, float tau, float* loss, float* coef, int32_t* bad, void* ws, hipStream_t st);
+hipError_t ssm_bwd(const float* Z, int64_t n_users, int64_t n_items, int C, const int64_t* u, const int64_t* cand,
+                   int64_t S, int K1, const float* coef, const float* grad_loss, float* dZ, void* ws,
+                   hipStream_t st);
+
 size_t gemm_tn_workspace_bytes(int64_t N, int M, int K, int nv);
 hipError_t gemm_tn(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t N, int M, int K, float* out,
                    float* colsum, const float* V, int64_t ldv, int nv, float* vout, void* ws, hipStream_t st);

@@ -253,6 +253,9 @@ RsPlan rs_plan(int64_t n, unsigned bits) {
   return pl;
 }
 
+}  // namespace
+
+// (shared with the sampled-softmax backward, ppgat_ssm.hip: declared in ppgat_internal.h)
 size_t rs_workspace_bytes(int64_t n, unsigned bits) {
   const RsPlan pl = rs_plan(n, bits);
   return 2 * align_up((size_t)pl.cells * 4) + align_up(pl.scan_bytes);
@@ -261,7 +264,7 @@ size_t rs_workspace_bytes(int64_t n, unsigned bits) {
 // sorts (k0, v0) using (k1, v1) as the ping-pong pair; *result_in_1 says where it ended.
 // mark != NULL: the last pass also sets mark[k] = 1 for every key k < mark_n.
 hipError_t rs_sort(int32_t* k0, int32_t* v0, int32_t* k1, int32_t* v1, int64_t n, unsigned bits, void* ws,
-                   bool* result_in_1, hipStream_t st, uint8_t* mark = nullptr, int64_t mark_n = 0) {
+                   bool* result_in_1, hipStream_t st, uint8_t* mark, int64_t mark_n) {
   const RsPlan pl = rs_plan(n, bits);
   char* p = static_cast<char*>(ws);
   int32_t* ghist = reinterpret_cast<int32_t*>(p);
@@ -288,6 +291,8 @@ hipError_t rs_sort(int32_t* k0, int32_t* v0, int32_t* k1, int32_t* v1, int64_t n
   *result_in_1 = in1;
   return hipGetLastError();
 }
+
+namespace {
 
 // contribution c = 4t + kind -> destination row (sort key)
 // (contributions of triples whose user row is -1 -- not held here -- get the sentinel key

@@ -1901,6 +1901,72 @@ def bpr_loss(Z: torch.Tensor, n_users: int, u, i, j, loss: str = "bpr", prepared
     return _BPRLoss.apply(Z, u, i, j, int(n_users), Z.size(0) - int(n_users), LOSS_KINDS[loss], None, prepared)
 
 
+class _SoftmaxLoss(torch.autograd.Function):
+    """Sampled-softmax loss (ppgat_ssm_fwd / ppgat_ssm_bwd).  No producer hand-off: the layer
+    that produced Z takes its ordinary backward prologue."""
+
+    @staticmethod
+    def forward(ctx, Z, u, cand, n_users: int, n_items: int, temperature: float):
+        lib = _lib.load()
+        # Z straight from a GATLayer: a hand-off an earlier consumer left on that node is stale
+        # for the gradient this loss returns -- dropped in backward, never made here
+        ctx.producer = _producer_of(Z, N=Z.size(0), C=Z.size(1))
+        Z = Z.contiguous()
+        _check_dev("Z", Z, torch.float32)
+        n_rows, C = Z.shape
+        S, K1 = cand.shape
+        u, cand = u.contiguous(), cand.contiguous()
+        _check_dev("u", u, torch.int64, Z.device)
+        _check_dev("cand", cand, torch.int64, Z.device)
+        _BadIndex.raise_pending()
+        ws, _ = _lib.workspace(lib.ppgat_ssm_workspace_bytes, n_rows, S, K1, C, device=Z.device)
+        loss = torch.empty(1, dtype=torch.float32, device=Z.device)
+        coef = torch.empty(max(S, 1), K1, dtype=torch.float32, device=Z.device)
+        bad = torch.empty(1, dtype=torch.int32, device=Z.device)
+        _lib.check(lib.ppgat_ssm_fwd(Z.data_ptr(), n_rows, n_users, n_items, C, u.data_ptr(), cand.data_ptr(), S, K1,
+                                     temperature, loss.data_ptr(), coef.data_ptr(), bad.data_ptr(), ws.data_ptr(),
+                                     ws.numel(), _lib.stream_handle(Z.device)), "ssm_fwd")
+        _BadIndex.track(bad)
+        ctx.save_for_backward(Z, u, cand, coef)
+        ctx.ws = ws
+        ctx.meta = (n_rows, n_users, n_items, C, S, K1, temperature)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, gl):
+        lib = _lib.load()
+        Z, u, cand, coef = ctx.saved_tensors
+        n_rows, n_users, n_items, C, S, K1, temperature = ctx.meta
+        gl = gl.reshape(1).to(torch.float32).contiguous()
+        dZ = torch.empty_like(Z)
+        prod, ctx.producer = ctx.producer, None
+        if prod is not None:
+            prod.pro_result = None
+        _lib.check(lib.ppgat_ssm_bwd(Z.data_ptr(), n_rows, n_users, n_items, C, u.data_ptr(), cand.data_ptr(), S, K1,
+                                     temperature, coef.data_ptr(), gl.data_ptr(), dZ.data_ptr(), ctx.ws.data_ptr(),
+                                     ctx.ws.numel(), _lib.stream_handle(Z.device)), "ssm_bwd")
+        ctx.ws = None
+        return dZ, None, None, None, None, None
+
+
+def softmax_loss(Z: torch.Tensor, n_users: int, u, cand, temperature: float = 1.0) -> torch.Tensor:
+    """Sampled-softmax loss: ``cand`` [S, M + 1] int64 item ids, column 0 the positive of user
+    ``u[t]``, the rest its sampled negatives (``BPRSampler.sample_candidates``);
+    ``mean_t(logsumexp_m s[t, m] - s[t, 0])`` with ``s = <Z[u], Z[n_users + cand]> / temperature``.
+    Fused forward and a deterministic backward (no float atomics)."""
+    if not isinstance(cand, torch.Tensor) or cand.dim() != 2 or cand.dtype != torch.int64 or cand.size(1) < 2:
+        raise ValueError("softmax_loss: cand must be a 2-D int64 tensor [S, M + 1] with at least 2 columns")
+    if not isinstance(u, torch.Tensor) or u.dtype != torch.int64 or u.numel() != cand.size(0):
+        raise ValueError("softmax_loss: u must be an int64 tensor with one user per row of cand")
+    temperature = float(temperature)
+    if not (temperature > 0.0 and temperature != float("inf")):
+        raise ValueError("softmax_loss: temperature must be finite and > 0")
+    _require(Z.is_cuda, "softmax_loss: ppgat runs on ROCm devices only; there is no CPU path")
+    if Z.dim() != 2 or Z.size(1) not in (32, 64, 128, 256):
+        raise NotImplementedError("softmax_loss: hidden size must be 32/64/128/256")
+    return _SoftmaxLoss.apply(Z, u.reshape(-1), cand, int(n_users), Z.size(0) - int(n_users), temperature)
+
+
 def bpr_loss_mapped(Z: torch.Tensor, n_users: int, n_items: int, row_map: torch.Tensor, u, i, j,
                     loss: str = "bpr", prepared: BprPrepared = None, grad_rows: int = 0,
                     grad_buf: Optional[torch.Tensor] = None) -> torch.Tensor:

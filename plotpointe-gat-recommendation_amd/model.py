@@ -165,3 +165,9 @@ def bpr_loss(Z: torch.Tensor, n_users: int, u, i, j, loss: str = "bpr", prepared
     device (ppgat_bpr_fwd / ppgat_bpr_bwd; with ``prepared`` from ``hip_ops.bpr_prepare`` the
     backward's triple sort has already run beside the forward)."""
     return hip_ops.bpr_loss(Z, n_users, u, i, j, loss, prepared=prepared)
+
+
+def softmax_loss(Z: torch.Tensor, n_users: int, u, cand, temperature: float = 1.0) -> torch.Tensor:
+    """Sampled-softmax loss of the positive ``cand[:, 0]`` against the negatives ``cand[:, 1:]``,
+    fused on the device (ppgat_ssm_fwd / ppgat_ssm_bwd)."""
+    return hip_ops.softmax_loss(Z, n_users, u, cand, temperature)

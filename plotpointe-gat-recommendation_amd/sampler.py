@@ -70,6 +70,13 @@ class BPRSampler:
                 raise ValueError("BPRSampler: a user holds (almost) every item; no negative found")
         return out[0], out[1], out[2]
 
+    def sample_candidates(self, samples: int, n_neg: int, seed: int = 42, offset: int = 0):
+        """-> (u [samples], cand [samples, n_neg + 1]) for ``hip_ops.softmax_loss``: the (u, i) of
+        ``sample(samples, seed, offset)`` and, per pair, ``eval_candidates(u, i, n_neg, seed)`` --
+        column 0 the positive i, then n_neg negatives outside u's train list.  No kernel of its own."""
+        u, i, _ = self.sample(samples, seed=seed, offset=offset)
+        return u, self.eval_candidates(u, i, n_neg, seed)
+
     def sample_positives(self, neg_per_pos: int, batch_size: int, batch: int, seed: int = 42, check: bool = True):
         """Mini-batch ``batch`` of an epoch of sample_bpr_batches (scripts/train_lightgcn.py:160-179)
         -> (u, i, j) int64 [S]: every train interaction in the order given (users in order, each

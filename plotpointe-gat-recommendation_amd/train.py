@@ -99,6 +99,8 @@ class Config:
     model_family: str = "gat_pyg"
     share_weights: bool = False  # gatv2_pyg: lin_r is lin_l
     edge_features: str = "none"  # gat_pyg: "rating" feeds (r - 1) / 4 per edge to GATConv(edge_dim=1)
+    negatives: int = 16          # loss "softmax": sampled negatives per positive (a convention, not tuned)
+    temperature: float = 1.0     # loss "softmax": the logits are <u, i> / temperature
 
 
 @dataclass
@@ -185,6 +187,22 @@ def check_edge_features(args):
                                   "implemented: the sharded layers take no edge features (--world-size 1)")
 
 
+def check_softmax_loss(args):
+    """--loss softmax: the GAT families on one GPU only; --negatives >= 1, --temperature > 0."""
+    if args.loss != "softmax":
+        return
+    if args.model_family == "lightgcn":
+        raise NotImplementedError("--loss softmax with --model-family lightgcn is not implemented: the LightGCN "
+                                  "trainer keeps its mini-batch BPR loss")
+    if args.world_size > 1:
+        raise NotImplementedError(f"--loss softmax with --world-size {args.world_size} is not implemented: the "
+                                  "sharded trainers take the BPR/BCE loss (--world-size 1)")
+    if args.negatives < 1:
+        raise ValueError("--negatives must be >= 1")
+    if not (args.temperature > 0 and args.temperature != float("inf")):
+        raise ValueError("--temperature must be finite and > 0")
+
+
 def build_model(cfg: Config, n_users: int, n_items: int, feat_dim: int):
     if cfg.model_family == "gat_pyg":
         return model_mod.PyGGAT(n_users, n_items, item_feat_dim=feat_dim, hidden=cfg.hidden_dim, layers=cfg.layers,
@@ -199,13 +217,23 @@ def build_model(cfg: Config, n_users: int, n_items: int, feat_dim: int):
     return m
 
 
-def epoch_step(model, opt, item_feats, edge_index, n_users: int, u, i, j, loss: str = "bpr", edge_attr=None):
+def epoch_step(model, opt, item_feats, edge_index, n_users: int, u, i, j, loss: str = "bpr", edge_attr=None,
+               softmax=None):
     """One epoch's optimisation step on one GPU (train_gat_custom.py:349-362, identical
     train_gat_pyg.py:307-323): the training forward over the whole graph, the BPR/BCE loss of
     the epoch's sampled triples, zero_grad, backward, ``opt.step()``.  Returns the loss.
     ``PPGAT_BPR_OVERLAP=1`` starts the loss backward's triple sort (it needs the triples only)
     on a side stream before the forward (hip_ops.bpr_prepare; measured no faster at config 2,
-    DESIGN.md section 4)."""
+    DESIGN.md section 4).  ``softmax`` = (cand [S, M + 1], temperature): the sampled-softmax loss of
+    those candidates (column 0 the positive of u) instead; ``loss``, i and j are then not used."""
+    if softmax is not None:
+        cand, temperature = softmax
+        Z = model(item_feats, edge_index) if edge_attr is None else model(item_feats, edge_index, edge_attr)
+        lo = model_mod.softmax_loss(Z, n_users, u, cand, temperature)
+        opt.zero_grad()
+        lo.backward()
+        opt.step()
+        return lo
     prep = None
     if os.environ.get("PPGAT_BPR_OVERLAP", "0") == "1":
         C = model.user_emb.weight.size(1)
@@ -428,7 +456,13 @@ def build_parser():
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--eval-neg-k", type=int, default=1000)
     ap.add_argument("--item-features", choices=["fused", "txt"], default="fused")
-    ap.add_argument("--loss", choices=["bpr", "bce"], default="bpr")
+    ap.add_argument("--loss", choices=["bpr", "bce", "softmax"], default="bpr",
+                    help="softmax: the sampled softmax of each positive against --negatives device-sampled "
+                         "negatives (GAT families, one GPU)")
+    ap.add_argument("--negatives", type=int, default=16,
+                    help="--loss softmax: negatives per positive; the default 16 is a convention, not a tuned value")
+    ap.add_argument("--temperature", type=float, default=1.0,
+                    help="--loss softmax: logits are <user, item> / temperature")
     ap.add_argument("--deterministic", action="store_true")
     ap.add_argument("--structured-logs", action="store_true")
     ap.add_argument("--fast-eval", action="store_true", help="vectorised negative sampling (same distribution)")
@@ -456,6 +490,7 @@ def build_parser():
 def main(argv=None):
     args = build_parser().parse_args(argv)
     check_edge_features(args)
+    check_softmax_loss(args)
     if args.recommend_out and args.world_size > 1:
         raise NotImplementedError("--recommend-out runs on one GPU (--world-size 1): the lists are made from the "
                                   "whole user and item tables")
@@ -474,7 +509,7 @@ def main(argv=None):
                  attn_dropout=args.attn_dropout, epochs=args.epochs, samples_per_epoch=args.samples_per_epoch,
                  seed=args.seed, eval_neg_k=args.eval_neg_k, item_features=args.item_features, loss=args.loss,
                  model_family=args.model_family, share_weights=args.share_weights,
-                 edge_features=args.edge_features)
+                 edge_features=args.edge_features, negatives=args.negatives, temperature=args.temperature)
     if args.lr is not None:
         cfg.lr = args.lr
     if args.l2 is not None:
@@ -537,7 +572,7 @@ def main(argv=None):
     best = -1.0
     val_metrics: Dict[str, float] = {}
     dev_sampler = None
-    if args.fast_sampler or args.device_eval or full:
+    if args.fast_sampler or args.device_eval or full or cfg.loss == "softmax":
         ptr, flat = user_csr(tr, n_users)
         dev_sampler = sampler_mod.BPRSampler(ptr, flat, n_items, device=device)
     for epoch in range(1, cfg.epochs + 1):
@@ -551,8 +586,11 @@ def main(argv=None):
             i = torch.from_numpy(i_arr).long().to(device)
             j = torch.from_numpy(j_arr).long().to(device)
         if sharded is None:
+            softmax = None
+            if cfg.loss == "softmax":  # the negatives always come from the device sampler
+                softmax = (dev_sampler.eval_candidates(u, i, cfg.negatives, seed=cfg.seed + epoch), cfg.temperature)
             loss_val = float(epoch_step(model, opt, item_feats, edge_index, n_users, u, i, j, cfg.loss,
-                                        edge_attr=edge_attr).item())
+                                        edge_attr=edge_attr, softmax=softmax).item())
         else:
             # each rank: its own users' triples (the sum over ranks is the reference's mean),
             # dense gradients all-reduced, user rows updated by their owner
@@ -599,6 +637,8 @@ def main(argv=None):
     out = {"best_val_ndcg@20": float(best), "val": val_metrics, "test": test_metrics, "config": cfg.__dict__,
            "notes": f"One-backward-per-epoch with S sampled BPR triples; features={cfg.item_features}; "
                     f"loss={cfg.loss}"}
+    if cfg.loss == "softmax":
+        out["notes"] += f" ({cfg.negatives} sampled negatives per positive, temperature {cfg.temperature})"
     if full:
         out["config"] = {**cfg.__dict__, "eval_mode": "full"}
         out["notes"] += "; " + FULL_EVAL_NOTE
