@@ -320,6 +320,41 @@ int ppgat_ssm_bwd(const float* Z, int64_t n_rows, int64_t n_users, int64_t n_ite
                   const int64_t* cand, int64_t n_samples, int64_t n_cand, float temperature, const float* coef,
                   const float* grad_loss, float* grad_Z, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- shared-negatives softmax loss: one pool of P items scored against every positive ----
+ * Replaces: nothing one-to-one -- the reference trains on one negative per positive
+ *           (scripts/train_gat_pyg.py:313-322).  In torch terms, with pool [P] ascending item ids
+ *           and hit [S, P] = (pool[None, :] == pos[:, None]) | (pool[j] in history(u[t])):
+ *             U = Z[u];  s0 = (U * Z[n_users + pos]).sum(-1) / temperature
+ *             s = (U @ Z[n_users + pool].T / temperature).masked_fill(hit, -inf)
+ *             loss = (torch.cat([s0[:, None], s], 1).logsumexp(1) - s0).mean()
+ *           and its autograd (matmul backward plus index_add_ with float atomics).
+ * Z [n_rows, C] with n_rows = n_users + n_items; u, pos int64 [S]; pool int64 [P], P >= 1,
+ * strictly ascending (so distinct).  hist_ptr int64 [n_users + 1] and hist_items int32, sorted
+ * per user (the sampler's arrays, as ppgat_full_rank takes them), nullable together: without them
+ * only a sample's own positive is masked.  The [S, P] scores are a split-bf16 matrix-core
+ * product at fp32 accuracy and are never written.  The forward writes the scalar mean loss,
+ * lse [S] and c0 [S] = (p0 - 1) / (S temperature), formed without cancellation, and leaves the
+ * mask words [S, ceil(P / 32)] in the workspace: the backward takes the SAME workspace,
+ * untouched since the forward.  A sample whose whole pool is masked has loss term 0 and c0 = 0.
+ * The backward recomputes the scores from Z and lse and writes every row of grad_Z [n_rows, C]
+ * (zero rows included) = grad_loss (a device scalar) times the sums of the contributions, without
+ * float atomics and in a fixed order: the same bits on every launch.  n_samples == 0: loss 0,
+ * zero gradient.  Indices outside their range are clamped and counted into bad_count[0]; pool
+ * entries not above their predecessor are counted into bad_count[1] (device int32[2], written
+ * by the forward).  channels in {64, 128} (ppgat_shs_supported); others: PPGAT_ERR_UNSUPPORTED
+ * before any device work.  Workspace (host only): O(S C + P C + S P / 8) bytes.
+ */
+int ppgat_shs_supported(int channels);
+int ppgat_shs_workspace_bytes(int64_t n_rows, int64_t n_samples, int64_t n_pool, int channels, size_t* bytes);
+int ppgat_shs_fwd(const float* Z, int64_t n_rows, int64_t n_users, int64_t n_items, int channels, const int64_t* u,
+                  const int64_t* pos, int64_t n_samples, const int64_t* pool, int64_t n_pool,
+                  const int64_t* hist_ptr, const int32_t* hist_items, float temperature, float* loss, float* lse,
+                  float* c0, int32_t* bad_count, void* workspace, size_t workspace_bytes, void* stream);
+int ppgat_shs_bwd(const float* Z, int64_t n_rows, int64_t n_users, int64_t n_items, int channels, const int64_t* u,
+                  const int64_t* pos, int64_t n_samples, const int64_t* pool, int64_t n_pool, float temperature,
+                  const float* lse, const float* c0, const float* grad_loss, float* grad_Z, void* workspace,
+                  size_t workspace_bytes, void* stream);
+
 /* ---- projection weight gradient ----------------------------------------------
  * Replaces: the weight (and bias) gradient of torch.nn.Linear in GATConv.lin /
  *           SimpleGATLayer.lin (train_gat_custom.py:66,77) and PyGGAT.item_proj

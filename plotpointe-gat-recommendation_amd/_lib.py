@@ -71,6 +71,12 @@ SIGNATURES = {
                               c_vp, c_sz, c_vp]),
     "ppgat_ssm_bwd": (c_int, [c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_i64, c_i64, c_f, c_vp, c_vp, c_vp,
                               c_vp, c_sz, c_vp]),
+    "ppgat_shs_supported": (c_int, [c_int]),
+    "ppgat_shs_workspace_bytes": (c_int, [c_i64, c_i64, c_i64, c_int, ctypes.POINTER(c_sz)]),
+    "ppgat_shs_fwd": (c_int, [c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_f,
+                              c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "ppgat_shs_bwd": (c_int, [c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_i64, c_vp, c_i64, c_f, c_vp, c_vp,
+                              c_vp, c_vp, c_vp, c_sz, c_vp]),
     "ppgat_gemm_tn_workspace_bytes": (c_int, [c_i64, c_int, c_int, c_int, ctypes.POINTER(c_sz)]),
     "ppgat_gemm_tn": (c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_int, c_vp,
                               c_vp, c_sz, c_vp]),

@@ -674,6 +674,69 @@ int ppgat_ssm_bwd(const float* Z, int64_t n_rows, int64_t n_users, int64_t n_ite
   return PPGAT_OK;
 }
 
+// ---- shared-negatives softmax loss ----
+static int check_shs(int64_t n_rows, int64_t n_users, int64_t n_items, int channels, int64_t S, int64_t P,
+                     float temperature, const char* who) {
+  if (!ppgat::shs_channels_ok(channels)) return fail(PPGAT_ERR_UNSUPPORTED, std::string(who) + ": channels must be 64/128");
+  if (P < 1) return fail(PPGAT_ERR_INVALID, std::string(who) + ": n_pool must be >= 1");
+  if (!(temperature > 0.f) || !std::isfinite(temperature))
+    return fail(PPGAT_ERR_INVALID, std::string(who) + ": temperature must be finite and > 0");
+  if (n_users < 1 || n_items < 1 || S < 0 || n_rows != n_users + n_items)
+    return fail(PPGAT_ERR_INVALID, std::string(who) + ": bad sizes (n_rows must be n_users + n_items)");
+  if (n_rows >= ((int64_t)1 << 31) - 1 || S >= ((int64_t)1 << 31) - 1 || P >= ((int64_t)1 << 31) - 1)
+    return fail(PPGAT_ERR_INVALID, std::string(who) + ": n_samples, n_pool and n_rows must be < 2^31 - 1");
+  return PPGAT_OK;
+}
+
+int ppgat_shs_supported(int channels) { return ppgat::shs_channels_ok(channels) ? 1 : 0; }
+
+int ppgat_shs_workspace_bytes(int64_t n_rows, int64_t n_samples, int64_t n_pool, int channels, size_t* bytes) {
+  if (!ppgat::shs_channels_ok(channels)) return fail(PPGAT_ERR_UNSUPPORTED, "shs_workspace_bytes: channels must be 64/128");
+  if (!bytes || n_rows < 0 || n_samples < 0 || n_pool < 1 || n_rows >= ((int64_t)1 << 31) - 1 ||
+      n_samples >= ((int64_t)1 << 31) - 1 || n_pool >= ((int64_t)1 << 31) - 1)
+    return fail(PPGAT_ERR_INVALID, "shs_workspace_bytes: bad arguments");
+  *bytes = ppgat::shs_workspace_bytes(n_rows, n_samples, n_pool, channels);
+  return PPGAT_OK;
+}
+
+int ppgat_shs_fwd(const float* Z, int64_t n_rows, int64_t n_users, int64_t n_items, int channels, const int64_t* u,
+                  const int64_t* pos, int64_t n_samples, const int64_t* pool, int64_t n_pool,
+                  const int64_t* hist_ptr, const int32_t* hist_items, float temperature, float* loss, float* lse,
+                  float* c0, int32_t* bad_count, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = check_shs(n_rows, n_users, n_items, channels, n_samples, n_pool, temperature, "shs_fwd")) return rc;
+  if (!Z || !loss || !pool || !bad_count || (n_samples > 0 && (!u || !pos || !lse || !c0)))
+    return fail(PPGAT_ERR_INVALID, "shs_fwd: null pointer");
+  if ((hist_ptr == nullptr) != (hist_items == nullptr))
+    return fail(PPGAT_ERR_INVALID, "shs_fwd: hist_ptr and hist_items must be given together");
+  if (!workspace || workspace_bytes < ppgat::shs_workspace_bytes(n_rows, n_samples, n_pool, channels))
+    return fail(PPGAT_ERR_INVALID, "shs_fwd: workspace too small");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = debug_range(u, 8, n_samples, 0, n_users, "shs_fwd: u", st)) return rc;
+  if (int rc = debug_range(pos, 8, n_samples, 0, n_items, "shs_fwd: pos", st)) return rc;
+  if (int rc = debug_range(pool, 8, n_pool, 0, n_items, "shs_fwd: pool", st)) return rc;
+  if (hist_ptr)
+    if (int rc = debug_range(hist_ptr, 8, n_users + 1, 0, ((int64_t)1 << 31), "shs_fwd: hist_ptr", st)) return rc;
+  hipError_t e = ppgat::shs_fwd(Z, n_users, n_items, channels, u, pos, n_samples, pool, n_pool, hist_ptr, hist_items,
+                                temperature, loss, lse, c0, bad_count, workspace, st);
+  if (e != hipSuccess) return hip_fail(e, "shs_fwd");
+  return PPGAT_OK;
+}
+
+int ppgat_shs_bwd(const float* Z, int64_t n_rows, int64_t n_users, int64_t n_items, int channels, const int64_t* u,
+                  const int64_t* pos, int64_t n_samples, const int64_t* pool, int64_t n_pool, float temperature,
+                  const float* lse, const float* c0, const float* grad_loss, float* grad_Z, void* workspace,
+                  size_t workspace_bytes, void* stream) {
+  if (int rc = check_shs(n_rows, n_users, n_items, channels, n_samples, n_pool, temperature, "shs_bwd")) return rc;
+  if (!Z || !grad_Z || !grad_loss || !pool || (n_samples > 0 && (!u || !pos || !lse || !c0)))
+    return fail(PPGAT_ERR_INVALID, "shs_bwd: null pointer");
+  if (!workspace || workspace_bytes < ppgat::shs_workspace_bytes(n_rows, n_samples, n_pool, channels))
+    return fail(PPGAT_ERR_INVALID, "shs_bwd: workspace too small");
+  hipError_t e = ppgat::shs_bwd(Z, n_users, n_items, channels, u, pos, n_samples, pool, n_pool, temperature, lse, c0,
+                                grad_loss, grad_Z, workspace, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail(e, "shs_bwd");
+  return PPGAT_OK;
+}
+
 int ppgat_bpr_bwd_producer(const float* Z, int64_t n_rows, int64_t n_users, int64_t n_items, int channels,
                            const int64_t* u, const int64_t* i, const int64_t* j, int64_t n_samples, const float* coef,
                            const float* grad_loss, float* grad_Z, const float* prev_bias, const float* prev_s_dst,

@@ -203,6 +203,18 @@ hipError_t sampled_rank(const float* Z, int64_t n_users, int64_t n_items, const 
                         const int64_t* users, const int64_t* cands, int64_t B, int64_t K1, int32_t* rank,
                         hipStream_t st);
 
+// shared-negatives softmax loss (ppgat_shs.hip): one ascending pool [P] scored against every
+// sample; uptr / hist nullable together; bad [2] = (out-of-range indices, pool entries out of
+// order); the backward takes the workspace the forward left (its mask words)
+bool shs_channels_ok(int C);
+size_t shs_workspace_bytes(int64_t N, int64_t S, int64_t P, int C);
+hipError_t shs_fwd(const float* Z, int64_t n_users, int64_t n_items, int C, const int64_t* u, const int64_t* pos,
+                   int64_t S, const int64_t* pool, int64_t P, const int64_t* uptr, const int32_t* hist, float tau,
+                   float* loss, float* lse, float* c0, int32_t* bad, void* ws, hipStream_t st);
+hipError_t shs_bwd(const float* Z, int64_t n_users, int64_t n_items, int C, const int64_t* u, const int64_t* pos,
+                   int64_t S, const int64_t* pool, int64_t P, float tau, const float* lse, const float* c0,
+                   const float* grad_loss, float* dZ, void* ws, hipStream_t st);
+
 // full-catalogue ranking (ppgat_fullrank.hip): rank / ties of pos[b] among every item outside
 // history(users[b]) + {pos[b]}; uptr / hist nullable together; ties nullable
 bool full_rank_channels_ok(int C);

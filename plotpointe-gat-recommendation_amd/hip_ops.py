@@ -1726,29 +1726,33 @@ class _BadIndex:
     pending = []
 
     @classmethod
-    def track(cls, bad: torch.Tensor):
+    def track(cls, bad: torch.Tensor, error=None):
+        """``error``: (exception type, message with one ``{}`` for the count) raised in place of
+        the IndexError when the count is not zero."""
         if torch.cuda.is_current_stream_capturing():  # a captured step: no host copy / event query
             return
         host = torch.empty(1, dtype=torch.int32, pin_memory=True)
         host.copy_(bad, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
-        cls.pending.append((ev, host))
+        cls.pending.append((ev, host, error))
 
     @classmethod
     def raise_pending(cls, wait: bool = False):
         if torch.cuda.is_current_stream_capturing():
             return
         keep = []
-        for ev, host in cls.pending:
+        for ev, host, error in cls.pending:
             if wait:
                 ev.synchronize()
             if wait or ev.query():
                 if int(host.item()) != 0:
                     cls.pending = []
+                    if error is not None:
+                        raise error[0](error[1].format(int(host.item())))
                     raise IndexError(f"bpr_loss: {int(host.item())} triples with u/i/j out of range")
             else:
-                keep.append((ev, host))
+                keep.append((ev, host, error))
         cls.pending = keep
 
 
@@ -1965,6 +1969,92 @@ def softmax_loss(Z: torch.Tensor, n_users: int, u, cand, temperature: float = 1.
     if Z.dim() != 2 or Z.size(1) not in (32, 64, 128, 256):
         raise NotImplementedError("softmax_loss: hidden size must be 32/64/128/256")
     return _SoftmaxLoss.apply(Z, u.reshape(-1), cand, int(n_users), Z.size(0) - int(n_users), temperature)
+
+
+class _SharedSoftmaxLoss(torch.autograd.Function):
+    """Shared-negatives softmax loss (ppgat_shs_fwd / ppgat_shs_bwd).  No producer hand-off: the
+    layer that produced Z takes its ordinary backward prologue."""
+
+    @staticmethod
+    def forward(ctx, Z, u, pos, pool, hist_ptr, hist_items, n_users: int, n_items: int, temperature: float):
+        lib = _lib.load()
+        # Z straight from a GATLayer: a hand-off an earlier consumer left on that node is stale
+        # for the gradient this loss returns -- dropped in backward, never made here
+        ctx.producer = _producer_of(Z, N=Z.size(0), C=Z.size(1))
+        Z = Z.contiguous()
+        _check_dev("Z", Z, torch.float32)
+        n_rows, C = Z.shape
+        S, P = u.numel(), pool.numel()
+        u, pos, pool = u.contiguous(), pos.contiguous(), pool.contiguous()
+        for name, t in (("u", u), ("pos", pos), ("pool", pool)):
+            _check_dev(name, t, torch.int64, Z.device)
+        if hist_ptr is not None:
+            _check_dev("history ptr", hist_ptr, torch.int64, Z.device)
+            _check_dev("history items", hist_items, torch.int32, Z.device)
+        _BadIndex.raise_pending()
+        ws, _ = _lib.workspace(lib.ppgat_shs_workspace_bytes, n_rows, S, P, C, device=Z.device)
+        loss = torch.empty(1, dtype=torch.float32, device=Z.device)
+        lse = torch.empty(max(S, 1), dtype=torch.float32, device=Z.device)
+        c0 = torch.empty(max(S, 1), dtype=torch.float32, device=Z.device)
+        bad = torch.empty(2, dtype=torch.int32, device=Z.device)
+        _lib.check(lib.ppgat_shs_fwd(Z.data_ptr(), n_rows, n_users, n_items, C, u.data_ptr(), pos.data_ptr(), S,
+                                     pool.data_ptr(), P, _lib.ptr(hist_ptr), _lib.ptr(hist_items), temperature,
+                                     loss.data_ptr(), lse.data_ptr(), c0.data_ptr(), bad.data_ptr(), ws.data_ptr(),
+                                     ws.numel(), _lib.stream_handle(Z.device)), "shs_fwd")
+        _BadIndex.track(bad[1:], (ValueError, "shared_softmax_loss: pool must be strictly ascending "
+                                              "({} entries not above their predecessor)"))
+        _BadIndex.track(bad[:1], (IndexError, "shared_softmax_loss: {} of u/pos/pool out of range"))
+        ctx.save_for_backward(Z, u, pos, pool, lse, c0)
+        ctx.ws = ws  # the mask words the forward left: the backward reads them
+        ctx.meta = (n_rows, n_users, n_items, C, S, P, temperature)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, gl):
+        lib = _lib.load()
+        Z, u, pos, pool, lse, c0 = ctx.saved_tensors
+        n_rows, n_users, n_items, C, S, P, temperature = ctx.meta
+        gl = gl.reshape(1).to(torch.float32).contiguous()
+        dZ = torch.empty_like(Z)
+        prod, ctx.producer = ctx.producer, None
+        if prod is not None:
+            prod.pro_result = None
+        _lib.check(lib.ppgat_shs_bwd(Z.data_ptr(), n_rows, n_users, n_items, C, u.data_ptr(), pos.data_ptr(), S,
+                                     pool.data_ptr(), P, temperature, lse.data_ptr(), c0.data_ptr(), gl.data_ptr(),
+                                     dZ.data_ptr(), ctx.ws.data_ptr(), ctx.ws.numel(),
+                                     _lib.stream_handle(Z.device)), "shs_bwd")
+        ctx.ws = None
+        return dZ, None, None, None, None, None, None, None, None
+
+
+def shared_softmax_loss(Z: torch.Tensor, n_users: int, u, pos, pool, temperature: float = 1.0,
+                        history=None) -> torch.Tensor:
+    """Softmax loss with negatives shared across the batch: every positive ``pos[t]`` of user
+    ``u[t]`` is scored against the same ``pool`` [P] of item ids (int64, strictly ascending, e.g.
+    ``BPRSampler.sample_pool``); ``mean_t(log(exp(s0) + sum_j exp(s[t, j])) - s0)`` over the pool
+    items that are neither the sample's positive nor in its user's ``history`` (a ``BPRSampler``
+    or its ``(ptr, items)`` pair; None: only the positive is masked).  The scores are a
+    matrix-core product that is never written; deterministic backward (no float atomics)."""
+    for name, t in (("u", u), ("pos", pos), ("pool", pool)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 1:
+            raise ValueError(f"shared_softmax_loss: {name} must be a 1-D int64 tensor")
+    if u.numel() != pos.numel():
+        raise ValueError("shared_softmax_loss: u and pos must have one entry per sample")
+    if pool.numel() < 1:
+        raise ValueError("shared_softmax_loss: pool must hold at least one item")
+    temperature = float(temperature)
+    if not (temperature > 0.0 and temperature != float("inf")):
+        raise ValueError("shared_softmax_loss: temperature must be finite and > 0")
+    _require(Z.is_cuda, "shared_softmax_loss: ppgat runs on ROCm devices only; there is no CPU path")
+    if Z.dim() != 2 or Z.size(1) not in (64, 128):
+        raise NotImplementedError("shared_softmax_loss: hidden size must be 64/128")
+    hist_ptr = hist_items = None
+    if history is not None:
+        hist_ptr, hist_items = (history.ptr, history.items) if hasattr(history, "ptr") else history
+        if hist_ptr.numel() != int(n_users) + 1:
+            raise ValueError("shared_softmax_loss: history ptr must have n_users + 1 entries")
+    return _SharedSoftmaxLoss.apply(Z, u, pos, pool, hist_ptr, hist_items, int(n_users), Z.size(0) - int(n_users),
+                                    temperature)
 
 
 def bpr_loss_mapped(Z: torch.Tensor, n_users: int, n_items: int, row_map: torch.Tensor, u, i, j,

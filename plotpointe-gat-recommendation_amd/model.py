@@ -171,3 +171,11 @@ def softmax_loss(Z: torch.Tensor, n_users: int, u, cand, temperature: float = 1.
     """Sampled-softmax loss of the positive ``cand[:, 0]`` against the negatives ``cand[:, 1:]``,
     fused on the device (ppgat_ssm_fwd / ppgat_ssm_bwd)."""
     return hip_ops.softmax_loss(Z, n_users, u, cand, temperature)
+
+
+def shared_softmax_loss(Z: torch.Tensor, n_users: int, u, pos, pool, temperature: float = 1.0,
+                        history=None) -> torch.Tensor:
+    """Softmax loss of the positives ``pos`` against one ``pool`` of item ids shared by every sample,
+    the sample's positive and its user's ``history`` masked out, fused on the device
+    (ppgat_shs_fwd / ppgat_shs_bwd)."""
+    return hip_ops.shared_softmax_loss(Z, n_users, u, pos, pool, temperature, history=history)

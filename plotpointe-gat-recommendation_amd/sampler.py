@@ -77,6 +77,17 @@ class BPRSampler:
         u, i, _ = self.sample(samples, seed=seed, offset=offset)
         return u, self.eval_candidates(u, i, n_neg, seed)
 
+    def sample_pool(self, n_pool: int, seed: int = 42) -> torch.Tensor:
+        """-> ``n_pool`` distinct item ids, uniform over the catalogue, ascending, int64 on the
+        sampler's device: the shared negatives of ``hip_ops.shared_softmax_loss``.  A seeded
+        torch permutation (not the hot path, no kernel of its own)."""
+        n_pool = int(n_pool)
+        if not 1 <= n_pool <= self.n_items:
+            raise ValueError(f"sample_pool: n_pool must be in [1, n_items = {self.n_items}], got {n_pool}")
+        gen = torch.Generator(device=self.device)
+        gen.manual_seed(int(seed) & 0x7FFFFFFFFFFFFFFF)
+        return torch.randperm(self.n_items, generator=gen, device=self.device)[:n_pool].sort().values.to(torch.int64)
+
     def sample_positives(self, neg_per_pos: int, batch_size: int, batch: int, seed: int = 42, check: bool = True):
         """Mini-batch ``batch`` of an epoch of sample_bpr_batches (scripts/train_lightgcn.py:160-179)
         -> (u, i, j) int64 [S]: every train interaction in the order given (users in order, each

@@ -188,7 +188,12 @@ def check_edge_features(args):
 
 
 def check_softmax_loss(args):
-    """--loss softmax: the GAT families on one GPU only; --negatives >= 1, --temperature > 0."""
+    """--loss softmax: the GAT families on one GPU only; --negatives >= 1, --temperature > 0.
+    --shared-negatives P > 0 (one pool per epoch instead of per-positive negatives) only with it."""
+    if args.shared_negatives < 0:
+        raise ValueError("--shared-negatives must be >= 0")
+    if args.shared_negatives > 0 and args.loss != "softmax":
+        raise ValueError(f"--shared-negatives {args.shared_negatives} needs --loss softmax (got --loss {args.loss})")
     if args.loss != "softmax":
         return
     if args.model_family == "lightgcn":
@@ -218,14 +223,24 @@ def build_model(cfg: Config, n_users: int, n_items: int, feat_dim: int):
 
 
 def epoch_step(model, opt, item_feats, edge_index, n_users: int, u, i, j, loss: str = "bpr", edge_attr=None,
-               softmax=None):
+               softmax=None, shared=None):
     """One epoch's optimisation step on one GPU (train_gat_custom.py:349-362, identical
     train_gat_pyg.py:307-323): the training forward over the whole graph, the BPR/BCE loss of
     the epoch's sampled triples, zero_grad, backward, ``opt.step()``.  Returns the loss.
     ``PPGAT_BPR_OVERLAP=1`` starts the loss backward's triple sort (it needs the triples only)
     on a side stream before the forward (hip_ops.bpr_prepare; measured no faster at config 2,
     DESIGN.md section 4).  ``softmax`` = (cand [S, M + 1], temperature): the sampled-softmax loss of
-    those candidates (column 0 the positive of u) instead; ``loss``, i and j are then not used."""
+    those candidates (column 0 the positive of u) instead; ``loss``, i and j are then not used.
+    ``shared`` = (pool [P], history, temperature): the shared-negatives softmax loss of the positives i
+    against that pool, ``history`` (the device sampler) excluded; ``loss`` and j are then not used."""
+    if shared is not None:
+        pool, history, temperature = shared
+        Z = model(item_feats, edge_index) if edge_attr is None else model(item_feats, edge_index, edge_attr)
+        lo = model_mod.shared_softmax_loss(Z, n_users, u, i, pool, temperature, history=history)
+        opt.zero_grad()
+        lo.backward()
+        opt.step()
+        return lo
     if softmax is not None:
         cand, temperature = softmax
         Z = model(item_feats, edge_index) if edge_attr is None else model(item_feats, edge_index, edge_attr)
@@ -460,7 +475,12 @@ def build_parser():
                     help="softmax: the sampled softmax of each positive against --negatives device-sampled "
                          "negatives (GAT families, one GPU)")
     ap.add_argument("--negatives", type=int, default=16,
-                    help="--loss softmax: negatives per positive; the default 16 is a convention, not a tuned value")
+                    help="--loss softmax: negatives per positive; the default 16 is a convention, not a tuned value "
+                         "(unused with --shared-negatives)")
+    ap.add_argument("--shared-negatives", type=int, default=0, metavar="P",
+                    help="--loss softmax: score every positive of an epoch against one pool of P items drawn per "
+                         "epoch (the user's train history excluded) instead of --negatives per-positive ones; "
+                         "0 = off")
     ap.add_argument("--temperature", type=float, default=1.0,
                     help="--loss softmax: logits are <user, item> / temperature")
     ap.add_argument("--deterministic", action="store_true")
@@ -537,6 +557,8 @@ def main(argv=None):
                   config={**cfg.__dict__, "device": str(device)})
     tr, va, te, n_users, n_items, feats_np = load_inputs(cfg, args.synthetic)
     print(f"[{tag}] n_users={n_users}, n_items={n_items}")
+    if args.shared_negatives > n_items:
+        raise ValueError(f"--shared-negatives {args.shared_negatives} exceeds the catalogue ({n_items} items)")
     edge_index = data.build_edge_index(n_users, n_items, tr).to(device)
     item_feats = torch.tensor(feats_np, dtype=torch.float32).to(device)
     assert item_feats.shape[0] == n_items
@@ -586,11 +608,14 @@ def main(argv=None):
             i = torch.from_numpy(i_arr).long().to(device)
             j = torch.from_numpy(j_arr).long().to(device)
         if sharded is None:
-            softmax = None
-            if cfg.loss == "softmax":  # the negatives always come from the device sampler
+            softmax = shared = None
+            if cfg.loss == "softmax" and args.shared_negatives > 0:  # one pool for the epoch's positives
+                shared = (dev_sampler.sample_pool(args.shared_negatives, cfg.seed + epoch), dev_sampler,
+                          cfg.temperature)
+            elif cfg.loss == "softmax":  # the negatives always come from the device sampler
                 softmax = (dev_sampler.eval_candidates(u, i, cfg.negatives, seed=cfg.seed + epoch), cfg.temperature)
             loss_val = float(epoch_step(model, opt, item_feats, edge_index, n_users, u, i, j, cfg.loss,
-                                        edge_attr=edge_attr, softmax=softmax).item())
+                                        edge_attr=edge_attr, softmax=softmax, shared=shared).item())
         else:
             # each rank: its own users' triples (the sum over ranks is the reference's mean),
             # dense gradients all-reduced, user rows updated by their owner
@@ -637,7 +662,10 @@ def main(argv=None):
     out = {"best_val_ndcg@20": float(best), "val": val_metrics, "test": test_metrics, "config": cfg.__dict__,
            "notes": f"One-backward-per-epoch with S sampled BPR triples; features={cfg.item_features}; "
                     f"loss={cfg.loss}"}
-    if cfg.loss == "softmax":
+    if cfg.loss == "softmax" and args.shared_negatives > 0:
+        out["notes"] += (f" ({args.shared_negatives} negatives shared across each epoch's positives, train history "
+                         f"excluded, temperature {cfg.temperature}; --negatives unused)")
+    elif cfg.loss == "softmax":
         out["notes"] += f" ({cfg.negatives} sampled negatives per positive, temperature {cfg.temperature})"
     if full:
         out["config"] = {**cfg.__dict__, "eval_mode": "full"}
