@@ -319,6 +319,14 @@ int ppgat_ssm_fwd(const float* Z, int64_t n_rows, int64_t n_users, int64_t n_ite
 int ppgat_ssm_bwd(const float* Z, int64_t n_rows, int64_t n_users, int64_t n_items, int channels, const int64_t* u,
                   const int64_t* cand, int64_t n_samples, int64_t n_cand, float temperature, const float* coef,
                   const float* grad_loss, float* grad_Z, void* workspace, size_t workspace_bytes, void* stream);
+/* The forward with a sampling correction (logQ): corr fp32 [n_items], finite, is subtracted from
+ * the logit of every negative, s[t, m] -= corr[cand[t, m]] for m >= 1, never from the
+ * positive's, before the online maximum is taken.  It carries no gradient, so coef is the
+ * softmax of the corrected logits and ppgat_ssm_bwd is the backward of this forward too. */
+int ppgat_ssm_fwd_corrected(const float* Z, int64_t n_rows, int64_t n_users, int64_t n_items, int channels,
+                            const int64_t* u, const int64_t* cand, const float* corr, int64_t n_samples,
+                            int64_t n_cand, float temperature, float* loss, float* coef, int32_t* bad_count,
+                            void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- shared-negatives softmax loss: one pool of P items scored against every positive ----
  * Replaces: nothing one-to-one -- the reference trains on one negative per positive
@@ -354,6 +362,24 @@ int ppgat_shs_bwd(const float* Z, int64_t n_rows, int64_t n_users, int64_t n_ite
                   const int64_t* pos, int64_t n_samples, const int64_t* pool, int64_t n_pool, float temperature,
                   const float* lse, const float* c0, const float* grad_loss, float* grad_Z, void* workspace,
                   size_t workspace_bytes, void* stream);
+/* The pair with a sampling correction (logQ): corr fp32 [n_items], finite, is subtracted from
+ * every pool logit, s[t, j] -= corr[pool[j]], never from the positive's s0.  corr[pool] is
+ * gathered once by the forward into its workspace (that of the _corrected size function, which
+ * the backward takes untouched, as above) and applied to the accumulator in the forward and in
+ * both backward sweeps in one association order, so the backward recomputes the forward's bits.
+ * No gradient flows to corr.  Everything else is as for the uncorrected pair. */
+int ppgat_shs_corrected_workspace_bytes(int64_t n_rows, int64_t n_samples, int64_t n_pool, int channels,
+                                        size_t* bytes);
+int ppgat_shs_fwd_corrected(const float* Z, int64_t n_rows, int64_t n_users, int64_t n_items, int channels,
+                            const int64_t* u, const int64_t* pos, int64_t n_samples, const int64_t* pool,
+                            int64_t n_pool, const int64_t* hist_ptr, const int32_t* hist_items, const float* corr,
+                            float temperature, float* loss, float* lse, float* c0, int32_t* bad_count,
+                            void* workspace, size_t workspace_bytes, void* stream);
+int ppgat_shs_bwd_corrected(const float* Z, int64_t n_rows, int64_t n_users, int64_t n_items, int channels,
+                            const int64_t* u, const int64_t* pos, int64_t n_samples, const int64_t* pool,
+                            int64_t n_pool, float temperature, const float* lse, const float* c0,
+                            const float* grad_loss, float* grad_Z, void* workspace, size_t workspace_bytes,
+                            void* stream);
 
 /* ---- projection weight gradient ----------------------------------------------
  * Replaces: the weight (and bias) gradient of torch.nn.Linear in GATConv.lin /
@@ -625,6 +651,28 @@ int ppgat_dynatt_bwd(const ppgat_schedule* src_sched, const ppgat_schedule* dst_
 int ppgat_eval_sample(const int64_t* user_ptr, const int32_t* items_sorted, const int64_t* users, const int64_t* pos,
                       int64_t n_eval, int64_t n_neg, int64_t n_items, uint64_t seed, int64_t* cands, int32_t* bad,
                       void* stream);
+
+/* ---- weighted draws: negatives in proportion to item weights ----------------------------
+ * Replaces: nothing in the reference, which draws every negative uniformly.
+ * cdf uint64 [n_items] (device): the inclusive prefix sum of integer item weights w_i >= 0
+ * quantised on the host, cdf[n_items - 1] = total > 0.  A draw is
+ *   r = mulhi64(draw64(seed, t, d), total);  item = the first i with cdf[i] > r
+ * (a binary search of the table), so item i comes with probability w_i / total exactly as far as
+ * the 64-bit stream is uniform, and an item of weight 0 never comes.
+ * ppgat_weighted_draws: out[n] = the draw (seed, t0 + n, 0), n < n_draws.
+ * ppgat_weighted_bpr_sample: ppgat_bpr_sample's contract; u and i are bit for bit what it gives
+ *   for the same (seed, t0 + s); j is the first weighted draw 2 + k outside u's items.
+ * ppgat_weighted_eval_sample: ppgat_eval_sample's contract with weighted draws d = 0, 1, ...
+ * 1024 draws at the most per negative, then 0 is written and *bad |= 2. */
+int ppgat_weighted_draws(const uint64_t* cdf, int64_t n_items, int64_t n_draws, uint64_t seed, int64_t t0,
+                         int64_t* out, void* stream);
+int ppgat_weighted_bpr_sample(const int64_t* user_ptr, const int32_t* items_sorted, const int32_t* eligible,
+                              const int64_t* n_eligible, int64_t n_items, const uint64_t* cdf, int64_t n_triples,
+                              uint64_t seed, int64_t t0, int64_t* u, int64_t* i, int64_t* j, int32_t* bad,
+                              void* stream);
+int ppgat_weighted_eval_sample(const int64_t* user_ptr, const int32_t* items_sorted, const int64_t* users,
+                               const int64_t* pos, int64_t n_eval, int64_t n_neg, int64_t n_items,
+                               const uint64_t* cdf, uint64_t seed, int64_t* cands, int32_t* bad, void* stream);
 
 /* ---- sampled ranking (evaluation) ------------------------------------------------
  * Replaces: the per-user loop of eval_sampled, scripts/train_gat_pyg.py:160-175:

@@ -71,12 +71,19 @@ SIGNATURES = {
                               c_vp, c_sz, c_vp]),
     "ppgat_ssm_bwd": (c_int, [c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_i64, c_i64, c_f, c_vp, c_vp, c_vp,
                               c_vp, c_sz, c_vp]),
+    "ppgat_ssm_fwd_corrected": (c_int, [c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_i64, c_i64, c_f, c_vp,
+                                        c_vp, c_vp, c_vp, c_sz, c_vp]),
     "ppgat_shs_supported": (c_int, [c_int]),
     "ppgat_shs_workspace_bytes": (c_int, [c_i64, c_i64, c_i64, c_int, ctypes.POINTER(c_sz)]),
     "ppgat_shs_fwd": (c_int, [c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_f,
                               c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "ppgat_shs_bwd": (c_int, [c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_i64, c_vp, c_i64, c_f, c_vp, c_vp,
                               c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "ppgat_shs_corrected_workspace_bytes": (c_int, [c_i64, c_i64, c_i64, c_int, ctypes.POINTER(c_sz)]),
+    "ppgat_shs_fwd_corrected": (c_int, [c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp,
+                                        c_vp, c_f, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "ppgat_shs_bwd_corrected": (c_int, [c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_i64, c_vp, c_i64, c_f, c_vp,
+                                        c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "ppgat_gemm_tn_workspace_bytes": (c_int, [c_i64, c_int, c_int, c_int, ctypes.POINTER(c_sz)]),
     "ppgat_gemm_tn": (c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_int, c_vp,
                               c_vp, c_sz, c_vp]),
@@ -131,6 +138,11 @@ SIGNATURES = {
     "ppgat_edge_dv_partial_rows": (c_i64, [c_i64]),
     "ppgat_edge_dv": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp]),
     "ppgat_eval_sample": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_u64, c_vp, c_vp, c_vp]),
+    "ppgat_weighted_draws": (c_int, [c_vp, c_i64, c_i64, c_u64, c_i64, c_vp, c_vp]),
+    "ppgat_weighted_bpr_sample": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_u64, c_i64, c_vp, c_vp, c_vp,
+                                          c_vp, c_vp]),
+    "ppgat_weighted_eval_sample": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_u64, c_vp, c_vp,
+                                           c_vp]),
     "ppgat_sampled_rank": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "ppgat_full_rank_supported": (c_int, [c_int]),
     "ppgat_full_rank_workspace_bytes": (c_int, [c_i64, c_i64, c_int, ctypes.POINTER(c_sz)]),

@@ -654,9 +654,28 @@ int ppgat_ssm_fwd(const float* Z, int64_t n_rows, int64_t n_users, int64_t n_ite
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (int rc = debug_range(u, 8, n_samples, 0, n_users, "ssm_fwd: u", st)) return rc;
   if (int rc = debug_range(cand, 8, n_samples * n_cand, 0, n_items, "ssm_fwd: cand", st)) return rc;
-  hipError_t e = ppgat::ssm_fwd(Z, n_users, n_items, channels, u, cand, n_samples, (int)n_cand, temperature, loss, coef,
-                                bad_count, workspace, st);
+  hipError_t e = ppgat::ssm_fwd(Z, n_users, n_items, channels, u, cand, nullptr, n_samples, (int)n_cand, temperature,
+                                loss, coef, bad_count, workspace, st);
   if (e != hipSuccess) return hip_fail(e, "ssm_fwd");
+  return PPGAT_OK;
+}
+
+int ppgat_ssm_fwd_corrected(const float* Z, int64_t n_rows, int64_t n_users, int64_t n_items, int channels,
+                            const int64_t* u, const int64_t* cand, const float* corr, int64_t n_samples,
+                            int64_t n_cand, float temperature, float* loss, float* coef, int32_t* bad_count,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = check_ssm(n_rows, n_users, n_items, channels, n_samples, n_cand, temperature, "ssm_fwd_corrected"))
+    return rc;
+  if (!Z || !loss || !corr || (n_samples > 0 && (!u || !cand || !coef)))
+    return fail(PPGAT_ERR_INVALID, "ssm_fwd_corrected: null pointer");
+  if (!workspace || workspace_bytes < ppgat::ssm_workspace_bytes(n_rows, n_samples, (int)n_cand, channels))
+    return fail(PPGAT_ERR_INVALID, "ssm_fwd_corrected: workspace too small");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = debug_range(u, 8, n_samples, 0, n_users, "ssm_fwd_corrected: u", st)) return rc;
+  if (int rc = debug_range(cand, 8, n_samples * n_cand, 0, n_items, "ssm_fwd_corrected: cand", st)) return rc;
+  hipError_t e = ppgat::ssm_fwd(Z, n_users, n_items, channels, u, cand, corr, n_samples, (int)n_cand, temperature, loss,
+                                coef, bad_count, workspace, st);
+  if (e != hipSuccess) return hip_fail(e, "ssm_fwd_corrected");
   return PPGAT_OK;
 }
 
@@ -717,7 +736,7 @@ int ppgat_shs_fwd(const float* Z, int64_t n_rows, int64_t n_users, int64_t n_ite
   if (hist_ptr)
     if (int rc = debug_range(hist_ptr, 8, n_users + 1, 0, ((int64_t)1 << 31), "shs_fwd: hist_ptr", st)) return rc;
   hipError_t e = ppgat::shs_fwd(Z, n_users, n_items, channels, u, pos, n_samples, pool, n_pool, hist_ptr, hist_items,
-                                temperature, loss, lse, c0, bad_count, workspace, st);
+                                nullptr, temperature, loss, lse, c0, bad_count, workspace, st);
   if (e != hipSuccess) return hip_fail(e, "shs_fwd");
   return PPGAT_OK;
 }
@@ -731,9 +750,63 @@ int ppgat_shs_bwd(const float* Z, int64_t n_rows, int64_t n_users, int64_t n_ite
     return fail(PPGAT_ERR_INVALID, "shs_bwd: null pointer");
   if (!workspace || workspace_bytes < ppgat::shs_workspace_bytes(n_rows, n_samples, n_pool, channels))
     return fail(PPGAT_ERR_INVALID, "shs_bwd: workspace too small");
-  hipError_t e = ppgat::shs_bwd(Z, n_users, n_items, channels, u, pos, n_samples, pool, n_pool, temperature, lse, c0,
-                                grad_loss, grad_Z, workspace, static_cast<hipStream_t>(stream));
+  hipError_t e = ppgat::shs_bwd(Z, n_users, n_items, channels, u, pos, n_samples, pool, n_pool, false, temperature, lse,
+                                c0, grad_loss, grad_Z, workspace, static_cast<hipStream_t>(stream));
   if (e != hipSuccess) return hip_fail(e, "shs_bwd");
+  return PPGAT_OK;
+}
+
+int ppgat_shs_corrected_workspace_bytes(int64_t n_rows, int64_t n_samples, int64_t n_pool, int channels,
+                                        size_t* bytes) {
+  if (!ppgat::shs_channels_ok(channels))
+    return fail(PPGAT_ERR_UNSUPPORTED, "shs_corrected_workspace_bytes: channels must be 64/128");
+  if (!bytes || n_rows < 0 || n_samples < 0 || n_pool < 1 || n_rows >= ((int64_t)1 << 31) - 1 ||
+      n_samples >= ((int64_t)1 << 31) - 1 || n_pool >= ((int64_t)1 << 31) - 1)
+    return fail(PPGAT_ERR_INVALID, "shs_corrected_workspace_bytes: bad arguments");
+  *bytes = ppgat::shs_corr_workspace_bytes(n_rows, n_samples, n_pool, channels);
+  return PPGAT_OK;
+}
+
+int ppgat_shs_fwd_corrected(const float* Z, int64_t n_rows, int64_t n_users, int64_t n_items, int channels,
+                            const int64_t* u, const int64_t* pos, int64_t n_samples, const int64_t* pool,
+                            int64_t n_pool, const int64_t* hist_ptr, const int32_t* hist_items, const float* corr,
+                            float temperature, float* loss, float* lse, float* c0, int32_t* bad_count,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = check_shs(n_rows, n_users, n_items, channels, n_samples, n_pool, temperature, "shs_fwd_corrected"))
+    return rc;
+  if (!Z || !loss || !pool || !bad_count || !corr || (n_samples > 0 && (!u || !pos || !lse || !c0)))
+    return fail(PPGAT_ERR_INVALID, "shs_fwd_corrected: null pointer");
+  if ((hist_ptr == nullptr) != (hist_items == nullptr))
+    return fail(PPGAT_ERR_INVALID, "shs_fwd_corrected: hist_ptr and hist_items must be given together");
+  if (!workspace || workspace_bytes < ppgat::shs_corr_workspace_bytes(n_rows, n_samples, n_pool, channels))
+    return fail(PPGAT_ERR_INVALID, "shs_fwd_corrected: workspace too small");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = debug_range(u, 8, n_samples, 0, n_users, "shs_fwd_corrected: u", st)) return rc;
+  if (int rc = debug_range(pos, 8, n_samples, 0, n_items, "shs_fwd_corrected: pos", st)) return rc;
+  if (int rc = debug_range(pool, 8, n_pool, 0, n_items, "shs_fwd_corrected: pool", st)) return rc;
+  if (hist_ptr)
+    if (int rc = debug_range(hist_ptr, 8, n_users + 1, 0, ((int64_t)1 << 31), "shs_fwd_corrected: hist_ptr", st))
+      return rc;
+  hipError_t e = ppgat::shs_fwd(Z, n_users, n_items, channels, u, pos, n_samples, pool, n_pool, hist_ptr, hist_items,
+                                corr, temperature, loss, lse, c0, bad_count, workspace, st);
+  if (e != hipSuccess) return hip_fail(e, "shs_fwd_corrected");
+  return PPGAT_OK;
+}
+
+int ppgat_shs_bwd_corrected(const float* Z, int64_t n_rows, int64_t n_users, int64_t n_items, int channels,
+                            const int64_t* u, const int64_t* pos, int64_t n_samples, const int64_t* pool,
+                            int64_t n_pool, float temperature, const float* lse, const float* c0,
+                            const float* grad_loss, float* grad_Z, void* workspace, size_t workspace_bytes,
+                            void* stream) {
+  if (int rc = check_shs(n_rows, n_users, n_items, channels, n_samples, n_pool, temperature, "shs_bwd_corrected"))
+    return rc;
+  if (!Z || !grad_Z || !grad_loss || !pool || (n_samples > 0 && (!u || !pos || !lse || !c0)))
+    return fail(PPGAT_ERR_INVALID, "shs_bwd_corrected: null pointer");
+  if (!workspace || workspace_bytes < ppgat::shs_corr_workspace_bytes(n_rows, n_samples, n_pool, channels))
+    return fail(PPGAT_ERR_INVALID, "shs_bwd_corrected: workspace too small");
+  hipError_t e = ppgat::shs_bwd(Z, n_users, n_items, channels, u, pos, n_samples, pool, n_pool, true, temperature, lse,
+                                c0, grad_loss, grad_Z, workspace, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail(e, "shs_bwd_corrected");
   return PPGAT_OK;
 }
 
@@ -1083,6 +1156,50 @@ int ppgat_bpr_sample_positives(const int64_t* user_ptr, const int32_t* user_item
   hipError_t e = ppgat::bpr_sample_positives(user_ptr, user_items, items_sorted, n_users, n_items, neg_per_pos,
                                              n_triples, seed, t0, u, i, j, bad, st);
   if (e != hipSuccess) return hip_fail(e, "bpr_sample_positives");
+  return PPGAT_OK;
+}
+
+// ---- weighted draws: items in proportion to quantised weights (cdf = their uint64 prefix sum) ----
+int ppgat_weighted_draws(const uint64_t* cdf, int64_t n_items, int64_t n_draws, uint64_t seed, int64_t t0,
+                         int64_t* out, void* stream) {
+  if (n_items < 1 || n_items > INT32_MAX || n_draws < 0 || t0 < 0)
+    return fail(PPGAT_ERR_INVALID, "weighted_draws: bad sizes");
+  if (!cdf || (n_draws > 0 && !out)) return fail(PPGAT_ERR_INVALID, "weighted_draws: null pointer");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  Timed t(PPGAT_K_SAMPLE, st);
+  hipError_t e = ppgat::weighted_draws(cdf, n_items, n_draws, seed, t0, out, st);
+  if (e != hipSuccess) return hip_fail(e, "weighted_draws");
+  return PPGAT_OK;
+}
+
+int ppgat_weighted_bpr_sample(const int64_t* user_ptr, const int32_t* items_sorted, const int32_t* eligible,
+                              const int64_t* n_eligible, int64_t n_items, const uint64_t* cdf, int64_t n_triples,
+                              uint64_t seed, int64_t t0, int64_t* u, int64_t* i, int64_t* j, int32_t* bad,
+                              void* stream) {
+  if (n_items < 1 || n_items > INT32_MAX || n_triples < 0 || t0 < 0)
+    return fail(PPGAT_ERR_INVALID, "weighted_bpr_sample: bad sizes");
+  if (!bad || !cdf || (n_triples > 0 && (!user_ptr || !eligible || !n_eligible || !u || !i || !j)))
+    return fail(PPGAT_ERR_INVALID, "weighted_bpr_sample: null pointer");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  Timed t(PPGAT_K_SAMPLE, st);
+  hipError_t e = ppgat::weighted_bpr_sample(user_ptr, items_sorted, eligible, n_eligible, n_items, cdf, n_triples, seed,
+                                            t0, u, i, j, bad, st);
+  if (e != hipSuccess) return hip_fail(e, "weighted_bpr_sample");
+  return PPGAT_OK;
+}
+
+int ppgat_weighted_eval_sample(const int64_t* user_ptr, const int32_t* items_sorted, const int64_t* users,
+                               const int64_t* pos, int64_t n_eval, int64_t n_neg, int64_t n_items,
+                               const uint64_t* cdf, uint64_t seed, int64_t* cands, int32_t* bad, void* stream) {
+  if (n_eval < 0 || n_neg < 0 || n_items < 1 || n_items > INT32_MAX)
+    return fail(PPGAT_ERR_INVALID, "weighted_eval_sample: sizes");
+  if (!bad || !cdf || (n_eval > 0 && (!user_ptr || !users || !pos || !cands)))
+    return fail(PPGAT_ERR_INVALID, "weighted_eval_sample: null");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  Timed t(PPGAT_K_SAMPLE, st);
+  hipError_t e = ppgat::weighted_eval_sample(user_ptr, items_sorted, users, pos, n_eval, n_neg, n_items, cdf, seed,
+                                             cands, bad, st);
+  if (e != hipSuccess) return hip_fail(e, "weighted_eval_sample");
   return PPGAT_OK;
 }
 

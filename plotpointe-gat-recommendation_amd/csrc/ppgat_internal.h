@@ -95,10 +95,12 @@ size_t rs_workspace_bytes(int64_t n, unsigned bits);
 hipError_t rs_sort(int32_t* k0, int32_t* v0, int32_t* k1, int32_t* v1, int64_t n, unsigned bits, void* ws,
                    bool* result_in_1, hipStream_t st, uint8_t* mark = nullptr, int64_t mark_n = 0);
 
-// sampled-softmax loss (ppgat_ssm.hip): cand [S, K1], column 0 the positive; n_rows = n_users + n_items
+// sampled-softmax loss (ppgat_ssm.hip): cand [S, K1], column 0 the positive; n_rows = n_users + n_items;
+// corr [n_items] nullable: subtracted from the logits of columns >= 1
 size_t ssm_workspace_bytes(int64_t N, int64_t S, int K1, int C);
 hipError_t ssm_fwd(const float* Z, int64_t n_users, int64_t n_items, int C, const int64_t* u, const int64_t* cand,
-                   int64_t S, int K1, float tau, float* loss, float* coef, int32_t* bad, void* ws, hipStream_t st);
+                   const float* corr, int64_t S, int K1, float tau, float* loss, float* coef, int32_t* bad, void* ws,
+                   hipStream_t st);
 hipError_t ssm_bwd(const float* Z, int64_t n_users, int64_t n_items, int C, const int64_t* u, const int64_t* cand,
                    int64_t S, int K1, const float* coef, const float* grad_loss, float* dZ, void* ws,
                    hipStream_t st);
@@ -195,6 +197,18 @@ hipError_t eval_sample(const int64_t* ptr, const int32_t* items_sorted, const in
                        int64_t n_eval, int64_t n_neg, int64_t n_items, uint64_t seed, int64_t* cands, int32_t* bad,
                        hipStream_t st);
 
+// weighted draws (ppgat_sample.hip): cdf [n_items] = inclusive uint64 prefix sum of the quantised
+// item weights, cdf[n_items - 1] > 0; the three keep the contracts of their uniform neighbours
+hipError_t weighted_draws(const uint64_t* cdf, int64_t n_items, int64_t n, uint64_t seed, int64_t t0, int64_t* out,
+                          hipStream_t st);
+hipError_t weighted_bpr_sample(const int64_t* ptr, const int32_t* items_sorted, const int32_t* eligible,
+                               const int64_t* n_eligible, int64_t n_items, const uint64_t* cdf, int64_t S,
+                               uint64_t seed, int64_t t0, int64_t* u, int64_t* i, int64_t* j, int32_t* bad,
+                               hipStream_t st);
+hipError_t weighted_eval_sample(const int64_t* ptr, const int32_t* items_sorted, const int64_t* users,
+                                const int64_t* pos, int64_t n_eval, int64_t n_neg, int64_t n_items,
+                                const uint64_t* cdf, uint64_t seed, int64_t* cands, int32_t* bad, hipStream_t st);
+
 // evaluation (ppgat_eval.hip)
 hipError_t serve_topk(const float* iv, int64_t n_items, int C, const int64_t* hptr, const int64_t* hist,
                       int64_t max_hist, int B, int k, float* U, float* scores, int32_t* out_idx, float* out_score,
@@ -207,13 +221,18 @@ hipError_t sampled_rank(const float* Z, int64_t n_users, int64_t n_items, const 
 // sample; uptr / hist nullable together; bad [2] = (out-of-range indices, pool entries out of
 // order); the backward takes the workspace the forward left (its mask words)
 bool shs_channels_ok(int C);
+// corr [n_items] nullable: subtracted from every pool logit; a corrected forward needs the
+// shs_corr_workspace_bytes workspace (it keeps corr[pool] behind the uncorrected layout) and its
+// backward is called with corrected = true
 size_t shs_workspace_bytes(int64_t N, int64_t S, int64_t P, int C);
+size_t shs_corr_workspace_bytes(int64_t N, int64_t S, int64_t P, int C);
 hipError_t shs_fwd(const float* Z, int64_t n_users, int64_t n_items, int C, const int64_t* u, const int64_t* pos,
-                   int64_t S, const int64_t* pool, int64_t P, const int64_t* uptr, const int32_t* hist, float tau,
-                   float* loss, float* lse, float* c0, int32_t* bad, void* ws, hipStream_t st);
+                   int64_t S, const int64_t* pool, int64_t P, const int64_t* uptr, const int32_t* hist,
+                   const float* corr, float tau, float* loss, float* lse, float* c0, int32_t* bad, void* ws,
+                   hipStream_t st);
 hipError_t shs_bwd(const float* Z, int64_t n_users, int64_t n_items, int C, const int64_t* u, const int64_t* pos,
-                   int64_t S, const int64_t* pool, int64_t P, float tau, const float* lse, const float* c0,
-                   const float* grad_loss, float* dZ, void* ws, hipStream_t st);
+                   int64_t S, const int64_t* pool, int64_t P, bool corrected, float tau, const float* lse,
+                   const float* c0, const float* grad_loss, float* dZ, void* ws, hipStream_t st);
 
 // full-catalogue ranking (ppgat_fullrank.hip): rank / ties of pos[b] among every item outside
 // history(users[b]) + {pos[b]}; uptr / hist nullable together; ties nullable

@@ -131,9 +131,16 @@ struct ShArg {
   const float* grad_loss;
   float scale;  // 1 / (S tau)
   float* G;     // USER: [S, C];  ITEM: [splits, P, C]
+  // CORR
+  const float* corrp;  // [P]: the correction of pool[j], gathered once per call (k_shs_corr)
 };
 
-template <int C, int MODE>
+// CORR (compile time, as EDGE in the GAT kernels): the logit of pool column j is
+// (acc * inv_tau) - corrp[j], in this association in all three sweeps, so the backward
+// recomputes the forward's bits.  FWD / USER stream the pool: the tile's corrections ride in the
+// LDS slots ITEM uses for the streamed lse.  ITEM owns the pool row: one register.  Without CORR
+// the instantiations are the kernels they were.
+template <int C, int MODE, bool CORR>
 __global__ void __launch_bounds__(ShCfg<C>::NT, 1) k_shs(ShArg a) {
   using F = ShCfg<C>;
   extern __shared__ __attribute__((aligned(16))) unsigned char sh_lds[];
@@ -187,6 +194,7 @@ __global__ void __launch_bounds__(ShCfg<C>::NT, 1) k_shs(ShArg a) {
     if (hf == 0 && b < NO) a.s0[b] = sp * a.inv_tau;
   }
   const float lse_own = MODE == SH_USER ? a.lse[bc] : 0.f;
+  const float corr_own = (CORR && ITEM) ? a.corrp[bc] : 0.f;
 
   float4 pf[F::UPT][2];
   float pf_lse = 0.f;
@@ -212,6 +220,11 @@ __global__ void __launch_bounds__(ShCfg<C>::NT, 1) k_shs(ShArg a) {
         const int64_t j = t * F::TN + row, wi = (int64_t)blockIdx.x * F::WAVES + w;
         pf_msk[k] = (j < NS && wi < W) ? a.mask[j * W + wi] : 0xffffffffu;  // rows / words outside: masked
       }
+    } else if (CORR) {
+      if (tid < F::TN) {
+        const int64_t j = t * F::TN + tid;
+        pf_lse = a.corrp[j < NS ? j : NS - 1];
+      }
     }
   };
   auto store_tile = [&](int bufi) {
@@ -229,6 +242,8 @@ __global__ void __launch_bounds__(ShCfg<C>::NT, 1) k_shs(ShArg a) {
       if (tid < F::TN) sLse[bufi * F::TN + tid] = pf_lse;
 #pragma unroll
       for (int k = 0; k < F::MPT; ++k) sMsk[bufi * F::TN * F::WAVES + tid + k * F::NT] = pf_msk[k];
+    } else if (CORR) {
+      if (tid < F::TN) sLse[bufi * F::TN + tid] = pf_lse;
     }
   };
 
@@ -275,12 +290,15 @@ __global__ void __launch_bounds__(ShCfg<C>::NT, 1) k_shs(ShArg a) {
       // accumulator q: streamed row 32 sb + (q & 3) + 8 (q >> 2) + 4 hf, owned column r
       if (MODE == SH_FWD) {
         const uint32_t m = mw[sb] >> (4 * hf);
+        const float* cs = sLse + bufi * F::TN + 32 * sb + 4 * hf;  // CORR: the streamed rows' corrections
         float sc[16];
         float tm = -INFINITY;
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-          const bool in = ((m >> ((q & 3) + 8 * (q >> 2))) & 1u) == 0u;
-          sc[q] = in ? acc[q] * a.inv_tau : -INFINITY;
+          const int row = (q & 3) + 8 * (q >> 2);
+          const bool in = ((m >> row) & 1u) == 0u;
+          const float lg = CORR ? acc[q] * a.inv_tau - cs[row] : acc[q] * a.inv_tau;
+          sc[q] = in ? lg : -INFINITY;
           tm = fmaxf(tm, sc[q]);
         }
         if (tm != -INFINITY) {
@@ -300,14 +318,18 @@ __global__ void __launch_bounds__(ShCfg<C>::NT, 1) k_shs(ShArg a) {
           for (int q = 0; q < 16; ++q) {
             const int row = (q & 3) + 8 * (q >> 2);
             const bool in = ((ms[row * F::WAVES] >> r) & 1u) == 0u;
-            p[q] = in ? __expf(acc[q] * a.inv_tau - ls[row]) : 0.f;
+            const float lg = CORR ? acc[q] * a.inv_tau - corr_own : acc[q] * a.inv_tau;
+            p[q] = in ? __expf(lg - ls[row]) : 0.f;
           }
         } else {
           const uint32_t m = mw[sb] >> (4 * hf);
+          const float* cs = sLse + bufi * F::TN + 32 * sb + 4 * hf;  // CORR: the streamed rows' corrections
 #pragma unroll
           for (int q = 0; q < 16; ++q) {
-            const bool in = ((m >> ((q & 3) + 8 * (q >> 2))) & 1u) == 0u;
-            p[q] = in ? __expf(acc[q] * a.inv_tau - lse_own) : 0.f;
+            const int row = (q & 3) + 8 * (q >> 2);
+            const bool in = ((m >> row) & 1u) == 0u;
+            const float lg = CORR ? acc[q] * a.inv_tau - cs[row] : acc[q] * a.inv_tau;
+            p[q] = in ? __expf(lg - lse_own) : 0.f;
           }
         }
         // the accumulator tile as the B operand: registers 8 s .. 8 s + 7 are k step s, element
@@ -432,6 +454,13 @@ __global__ void __launch_bounds__(256) k_shs_mask(const int64_t* __restrict__ u,
   }
   if (nbad) atomicAdd(bad, nbad);  // (integer counts: exact in any order)
   if (nord) atomicAdd(bad + 1, nord);
+}
+
+// corrp[j] = corr[pool[j]] (clamped like every other use of the pool), once per call
+__global__ void __launch_bounds__(256) k_shs_corr(const float* __restrict__ corr, const int64_t* __restrict__ pool,
+                                                  int64_t P, int64_t n_items, float* __restrict__ corrp) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < P) corrp[j] = corr[sh_clamp(pool[j], n_items)];
 }
 
 // ---------------------------------------------------------------------------
@@ -733,23 +762,37 @@ ShWs sh_ws(void* ws, int64_t N, int64_t S, int64_t P, int C) {
   return w;
 }
 
-template <int C, int MODE>
-hipError_t sh_launch(const ShArg& a, int64_t otiles, int64_t nsplit, hipStream_t st) {
+template <int C, int MODE, bool CORR>
+hipError_t sh_launch_c(const ShArg& a, int64_t otiles, int64_t nsplit, hipStream_t st) {
   using F = ShCfg<C>;
-  const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shs<C, MODE>),
+  const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shs<C, MODE, CORR>),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)F::LDS);
   if (attr != hipSuccess) return attr;
   if (otiles > 0x7fffffff || nsplit > 65535) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((k_shs<C, MODE>), dim3((unsigned)otiles, (unsigned)nsplit), dim3(F::NT), F::LDS, st, a);
+  hipLaunchKernelGGL((k_shs<C, MODE, CORR>), dim3((unsigned)otiles, (unsigned)nsplit), dim3(F::NT), F::LDS, st, a);
   return hipGetLastError();
+}
+
+template <int C, int MODE>
+hipError_t sh_launch(const ShArg& a, int64_t otiles, int64_t nsplit, hipStream_t st) {
+  return a.corrp != nullptr ? sh_launch_c<C, MODE, true>(a, otiles, nsplit, st)
+                            : sh_launch_c<C, MODE, false>(a, otiles, nsplit, st);
+}
+
+// the gathered corrections sit behind the uncorrected layout, which stays what it was
+float* sh_corrp(void* ws, int64_t N, int64_t S, int64_t P, int C) {
+  return reinterpret_cast<float*>(static_cast<char*>(ws) + sh_ws(nullptr, N, S, P, C).bytes);
 }
 
 template <int C>
 hipError_t sh_fwd(const float* Z, int64_t n_users, int64_t n_items, const int64_t* u, const int64_t* pos, int64_t S,
-                  const int64_t* pool, int64_t P, const int64_t* uptr, const int32_t* hist, float tau, float* loss,
-                  float* lse, float* c0, int32_t* bad, void* ws, hipStream_t st) {
+                  const int64_t* pool, int64_t P, const int64_t* uptr, const int32_t* hist, const float* corr,
+                  float tau, float* loss, float* lse, float* c0, int32_t* bad, void* ws, hipStream_t st) {
   using F = ShCfg<C>;
   const ShWs w = sh_ws(ws, n_users + n_items, S, P, C);
+  float* corrp = corr != nullptr ? sh_corrp(ws, n_users + n_items, S, P, C) : nullptr;
+  if (corrp != nullptr)
+    hipLaunchKernelGGL(k_shs_corr, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, corr, pool, P, n_items, corrp);
   const int64_t W = (P + 31) / 32;
   const int64_t n16 = S > 0 ? (int64_t)((w.mask_bytes + 15) / 16) : 0;
   hipLaunchKernelGGL(k_shs_clear, dim3((unsigned)((n16 + 255) / 256 + 1)), dim3(256), 0, st,
@@ -764,7 +807,7 @@ hipError_t sh_fwd(const float* Z, int64_t n_users, int64_t n_items, const int64_
     ShArg a{};
     a.Z = Z; a.n_users = n_users; a.n_items = n_items; a.u = u; a.pos = pos; a.pool = pool;
     a.S = S; a.P = P; a.W = W; a.mask = w.mask; a.inv_tau = 1.f / tau; a.tiles_per_split = sp.tiles_per_split;
-    a.pm = w.pm; a.pl = w.pl; a.s0 = w.s0;
+    a.pm = w.pm; a.pl = w.pl; a.s0 = w.s0; a.corrp = corrp;
     e = sh_launch<C, SH_FWD>(a, (S + F::TM - 1) / F::TM, sp.n, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_shs_finish, dim3((unsigned)nb), dim3(256), 0, st, w.pm, w.pl, w.s0, S, (int)sp.n,
@@ -777,7 +820,7 @@ hipError_t sh_fwd(const float* Z, int64_t n_users, int64_t n_items, const int64_
 
 template <int C>
 hipError_t sh_bwd(const float* Z, int64_t n_users, int64_t n_items, const int64_t* u, const int64_t* pos, int64_t S,
-                  const int64_t* pool, int64_t P, float tau, const float* lse, const float* c0,
+                  const int64_t* pool, int64_t P, bool corrected, float tau, const float* lse, const float* c0,
                   const float* grad_loss, float* dZ, void* ws, hipStream_t st) {
   using F = ShCfg<C>;
   using G = ShGeo<C>;
@@ -787,6 +830,7 @@ hipError_t sh_bwd(const float* Z, int64_t n_users, int64_t n_items, const int64_
   a.Z = Z; a.n_users = n_users; a.n_items = n_items; a.u = u; a.pos = pos; a.pool = pool;
   a.S = S; a.P = P; a.W = (P + 31) / 32; a.mask = w.mask; a.inv_tau = 1.f / tau;
   a.lse = lse; a.c0 = c0; a.grad_loss = grad_loss; a.scale = 1.f / ((float)S * tau);
+  a.corrp = corrected ? sh_corrp(ws, N, S, P, C) : nullptr;  // (the forward's gather, like its mask words)
   // the two sweeps
   a.G = w.Gu;
   a.tiles_per_split = (P + F::TN - 1) / F::TN;
@@ -832,23 +876,32 @@ bool shs_channels_ok(int C) { return C == 64 || C == 128; }
 
 size_t shs_workspace_bytes(int64_t N, int64_t S, int64_t P, int C) { return sh_ws(nullptr, N, S, P, C).bytes; }
 
+size_t shs_corr_workspace_bytes(int64_t N, int64_t S, int64_t P, int C) {
+  return sh_ws(nullptr, N, S, P, C).bytes + sh_align((size_t)(P > 0 ? P : 1) * 4);
+}
+
 hipError_t shs_fwd(const float* Z, int64_t n_users, int64_t n_items, int C, const int64_t* u, const int64_t* pos,
-                   int64_t S, const int64_t* pool, int64_t P, const int64_t* uptr, const int32_t* hist, float tau,
-                   float* loss, float* lse, float* c0, int32_t* bad, void* ws, hipStream_t st) {
+                   int64_t S, const int64_t* pool, int64_t P, const int64_t* uptr, const int32_t* hist,
+                   const float* corr, float tau, float* loss, float* lse, float* c0, int32_t* bad, void* ws,
+                   hipStream_t st) {
   switch (C) {
-    case 64: return sh_fwd<64>(Z, n_users, n_items, u, pos, S, pool, P, uptr, hist, tau, loss, lse, c0, bad, ws, st);
-    case 128: return sh_fwd<128>(Z, n_users, n_items, u, pos, S, pool, P, uptr, hist, tau, loss, lse, c0, bad, ws, st);
+    case 64:
+      return sh_fwd<64>(Z, n_users, n_items, u, pos, S, pool, P, uptr, hist, corr, tau, loss, lse, c0, bad, ws, st);
+    case 128:
+      return sh_fwd<128>(Z, n_users, n_items, u, pos, S, pool, P, uptr, hist, corr, tau, loss, lse, c0, bad, ws, st);
     default: return hipErrorInvalidValue;
   }
 }
 
 hipError_t shs_bwd(const float* Z, int64_t n_users, int64_t n_items, int C, const int64_t* u, const int64_t* pos,
-                   int64_t S, const int64_t* pool, int64_t P, float tau, const float* lse, const float* c0,
-                   const float* grad_loss, float* dZ, void* ws, hipStream_t st) {
+                   int64_t S, const int64_t* pool, int64_t P, bool corrected, float tau, const float* lse,
+                   const float* c0, const float* grad_loss, float* dZ, void* ws, hipStream_t st) {
   if (S == 0) return hipMemsetAsync(dZ, 0, (size_t)(n_users + n_items) * C * 4, st);
   switch (C) {
-    case 64: return sh_bwd<64>(Z, n_users, n_items, u, pos, S, pool, P, tau, lse, c0, grad_loss, dZ, ws, st);
-    case 128: return sh_bwd<128>(Z, n_users, n_items, u, pos, S, pool, P, tau, lse, c0, grad_loss, dZ, ws, st);
+    case 64:
+      return sh_bwd<64>(Z, n_users, n_items, u, pos, S, pool, P, corrected, tau, lse, c0, grad_loss, dZ, ws, st);
+    case 128:
+      return sh_bwd<128>(Z, n_users, n_items, u, pos, S, pool, P, corrected, tau, lse, c0, grad_loss, dZ, ws, st);
     default: return hipErrorInvalidValue;
   }
 }

@@ -79,10 +79,15 @@ __device__ __forceinline__ void merge_ml(float& m, float& l, float mo, float lo)
 // ---------------------------------------------------------------------------
 // forward: one wave per sample
 // ---------------------------------------------------------------------------
-template <int C>
+// CORR: corr [n_items] is subtracted from the logit of every negative (columns >= 1; never from
+// the positive's) as the score is formed, so it is inside the online (max, sum) and inside the
+// scores pass 2 reads back: coef is the softmax of the corrected logits and the backward is the
+// uncorrected one's.  Without CORR the kernel is the one it was.
+template <int C, bool CORR>
 __global__ void __launch_bounds__(256) k_ssm_fwd(const float* __restrict__ Z, int64_t n_users, int64_t n_items,
                                                  const int64_t* __restrict__ u, const int64_t* __restrict__ cand,
-                                                 int64_t S, int K1, float tau, float* coef,
+                                                 const float* __restrict__ corr, int64_t S, int K1, float tau,
+                                                 float* coef,
                                                  float* __restrict__ block_loss, int32_t* __restrict__ block_bad) {
   using G = Geo<C>;
   constexpr int LPR = G::LPR, EPW = G::EPW, U = G::U;
@@ -106,21 +111,24 @@ __global__ void __launch_bounds__(256) k_ssm_fwd(const float* __restrict__ Z, in
     // pass 1: candidate mb + k EPW + sg for k < U; lane sl == k of the subgroup keeps its score
     for (int mb = 0; mb < K1; mb += EPW * U) {
       float4 v[U];
+      float cr[U];  // CORR: the candidates' correction terms (0 for the positive)
 #pragma unroll
       for (int k = 0; k < U; ++k) {
         const int m = mb + k * EPW + sg;
         v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+        cr[k] = 0.f;
         if (m < K1) {
           const int64_t id = cand[base + m];
           if (sl == 0 && (id < 0 || id >= n_items)) ++nbad;
           v[k] = ld4(Z + (n_users + clamp_idx(id, n_items)) * C + sl * 4);
+          if (CORR && m > 0) cr[k] = corr[clamp_idx(id, n_items)];
         }
       }
 #pragma unroll
       for (int k = 0; k < U; ++k) {
         const int m = mb + k * EPW + sg;
         const float d = group_reduce<Op::Sum, 1, LPR / 2>(dot4(a, v[k]));  // (every lane: DPP / permlane steps)
-        const float s = d / tau;
+        const float s = CORR ? d / tau - cr[k] : d / tau;
         if (m < K1) {
           if (sl == k) coef[base + m] = s;
           if (m == 0) s0 = s;
@@ -411,12 +419,16 @@ SsmWs ssm_ws(void* ws, int64_t N, int64_t S, int K1, int C) {
 size_t ssm_workspace_bytes(int64_t N, int64_t S, int K1, int C) { return ssm_ws(nullptr, N, S, K1, C).bytes; }
 
 hipError_t ssm_fwd(const float* Z, int64_t n_users, int64_t n_items, int C, const int64_t* u, const int64_t* cand,
-                   int64_t S, int K1, float tau, float* loss, float* coef, int32_t* bad, void* ws, hipStream_t st) {
+                   const float* corr, int64_t S, int K1, float tau, float* loss, float* coef, int32_t* bad, void* ws,
+                   hipStream_t st) {
   const SsmWs w = ssm_ws(ws, n_users + n_items, S, K1, C);
   const int64_t nb = ssm_fwd_blocks(S);
-  if (S > 0) {
-    PPGAT_DISPATCH_SSM_C(C, hipLaunchKernelGGL(k_ssm_fwd<CC>, dim3((unsigned)nb), dim3(256), 0, st, Z, n_users, n_items,
-                                               u, cand, S, K1, tau, coef, w.block_loss, w.block_bad));
+  if (S > 0 && corr != nullptr) {
+    PPGAT_DISPATCH_SSM_C(C, hipLaunchKernelGGL((k_ssm_fwd<CC, true>), dim3((unsigned)nb), dim3(256), 0, st, Z, n_users,
+                                               n_items, u, cand, corr, S, K1, tau, coef, w.block_loss, w.block_bad));
+  } else if (S > 0) {
+    PPGAT_DISPATCH_SSM_C(C, hipLaunchKernelGGL((k_ssm_fwd<CC, false>), dim3((unsigned)nb), dim3(256), 0, st, Z, n_users,
+                                               n_items, u, cand, corr, S, K1, tau, coef, w.block_loss, w.block_bad));
   }
   hipLaunchKernelGGL(k_ssm_loss, dim3(1), dim3(1024), 0, st, w.block_loss, w.block_bad, S > 0 ? nb : 0,
                      S > 0 ? (float)S : 1.f, loss, bad);

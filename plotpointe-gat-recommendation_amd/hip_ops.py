@@ -1905,12 +1905,32 @@ def bpr_loss(Z: torch.Tensor, n_users: int, u, i, j, loss: str = "bpr", prepared
     return _BPRLoss.apply(Z, u, i, j, int(n_users), Z.size(0) - int(n_users), LOSS_KINDS[loss], None, prepared)
 
 
+def _check_correction(who: str, correction, Z: torch.Tensor, n_items: int) -> torch.Tensor:
+    """The logQ table of a softmax loss: fp32 [n_items] on Z's device, no gradient (raises before
+    any launch otherwise)."""
+    if not isinstance(correction, torch.Tensor) or correction.dtype != torch.float32 or correction.dim() != 1:
+        raise ValueError(f"{who}: correction must be a 1-D float32 tensor")
+    if correction.numel() != n_items:
+        raise ValueError(f"{who}: correction must have one entry per item ({n_items}), got {correction.numel()}")
+    if correction.device != Z.device:
+        raise ValueError(f"{who}: correction must be on Z's device ({Z.device}), got {correction.device}")
+    return correction.detach().contiguous()
+
+
+def _track_correction(who: str, used: torch.Tensor):
+    """One device check of the correction terms a call subtracts (``used`` = correction[negatives]):
+    -inf (an item the sampler never draws) and NaN are refused, deferred like the index checks."""
+    bad = (~(used > float("-inf"))).sum().to(torch.int32).reshape(1)  # NaN > -inf is False too
+    _BadIndex.track(bad, (ValueError, who + ": {} correction terms of sampled negatives are -inf or NaN (an item of "
+                                            "zero sampling weight among the negatives?)"))
+
+
 class _SoftmaxLoss(torch.autograd.Function):
     """Sampled-softmax loss (ppgat_ssm_fwd / ppgat_ssm_bwd).  No producer hand-off: the layer
     that produced Z takes its ordinary backward prologue."""
 
     @staticmethod
-    def forward(ctx, Z, u, cand, n_users: int, n_items: int, temperature: float):
+    def forward(ctx, Z, u, cand, n_users: int, n_items: int, temperature: float, corr=None):
         lib = _lib.load()
         # Z straight from a GATLayer: a hand-off an earlier consumer left on that node is stale
         # for the gradient this loss returns -- dropped in backward, never made here
@@ -1927,13 +1947,22 @@ class _SoftmaxLoss(torch.autograd.Function):
         loss = torch.empty(1, dtype=torch.float32, device=Z.device)
         coef = torch.empty(max(S, 1), K1, dtype=torch.float32, device=Z.device)
         bad = torch.empty(1, dtype=torch.int32, device=Z.device)
-        _lib.check(lib.ppgat_ssm_fwd(Z.data_ptr(), n_rows, n_users, n_items, C, u.data_ptr(), cand.data_ptr(), S, K1,
-                                     temperature, loss.data_ptr(), coef.data_ptr(), bad.data_ptr(), ws.data_ptr(),
-                                     ws.numel(), _lib.stream_handle(Z.device)), "ssm_fwd")
+        if corr is None:
+            _lib.check(lib.ppgat_ssm_fwd(Z.data_ptr(), n_rows, n_users, n_items, C, u.data_ptr(), cand.data_ptr(), S,
+                                         K1, temperature, loss.data_ptr(), coef.data_ptr(), bad.data_ptr(),
+                                         ws.data_ptr(), ws.numel(), _lib.stream_handle(Z.device)), "ssm_fwd")
+        else:
+            if S > 0:
+                _track_correction("softmax_loss", corr[cand[:, 1:].clamp(0, n_items - 1)])
+            _lib.check(lib.ppgat_ssm_fwd_corrected(Z.data_ptr(), n_rows, n_users, n_items, C, u.data_ptr(),
+                                                   cand.data_ptr(), corr.data_ptr(), S, K1, temperature,
+                                                   loss.data_ptr(), coef.data_ptr(), bad.data_ptr(), ws.data_ptr(),
+                                                   ws.numel(), _lib.stream_handle(Z.device)), "ssm_fwd_corrected")
         _BadIndex.track(bad)
         ctx.save_for_backward(Z, u, cand, coef)
         ctx.ws = ws
         ctx.meta = (n_rows, n_users, n_items, C, S, K1, temperature)
+        ctx.corrected = corr is not None
         return loss.view(())
 
     @staticmethod
@@ -1950,14 +1979,17 @@ class _SoftmaxLoss(torch.autograd.Function):
                                      temperature, coef.data_ptr(), gl.data_ptr(), dZ.data_ptr(), ctx.ws.data_ptr(),
                                      ctx.ws.numel(), _lib.stream_handle(Z.device)), "ssm_bwd")
         ctx.ws = None
-        return dZ, None, None, None, None, None
+        return (dZ,) + (None,) * (6 if ctx.corrected else 5)  # (one per input of this apply)
 
 
-def softmax_loss(Z: torch.Tensor, n_users: int, u, cand, temperature: float = 1.0) -> torch.Tensor:
+def softmax_loss(Z: torch.Tensor, n_users: int, u, cand, temperature: float = 1.0, correction=None) -> torch.Tensor:
     """Sampled-softmax loss: ``cand`` [S, M + 1] int64 item ids, column 0 the positive of user
     ``u[t]``, the rest its sampled negatives (``BPRSampler.sample_candidates``);
     ``mean_t(logsumexp_m s[t, m] - s[t, 0])`` with ``s = <Z[u], Z[n_users + cand]> / temperature``.
-    Fused forward and a deterministic backward (no float atomics)."""
+    Fused forward and a deterministic backward (no float atomics).
+    ``correction`` (fp32 [n_items], e.g. ``BPRSampler.correction(M)``): the logQ term of negatives
+    that were not drawn uniformly, ``s[t, m] -= correction[cand[t, m]]`` for m >= 1, never for the
+    positive; it takes no gradient, and the terms the call uses must not be -inf or NaN."""
     if not isinstance(cand, torch.Tensor) or cand.dim() != 2 or cand.dtype != torch.int64 or cand.size(1) < 2:
         raise ValueError("softmax_loss: cand must be a 2-D int64 tensor [S, M + 1] with at least 2 columns")
     if not isinstance(u, torch.Tensor) or u.dtype != torch.int64 or u.numel() != cand.size(0):
@@ -1968,7 +2000,10 @@ def softmax_loss(Z: torch.Tensor, n_users: int, u, cand, temperature: float = 1.
     _require(Z.is_cuda, "softmax_loss: ppgat runs on ROCm devices only; there is no CPU path")
     if Z.dim() != 2 or Z.size(1) not in (32, 64, 128, 256):
         raise NotImplementedError("softmax_loss: hidden size must be 32/64/128/256")
-    return _SoftmaxLoss.apply(Z, u.reshape(-1), cand, int(n_users), Z.size(0) - int(n_users), temperature)
+    if correction is None:
+        return _SoftmaxLoss.apply(Z, u.reshape(-1), cand, int(n_users), Z.size(0) - int(n_users), temperature)
+    corr = _check_correction("softmax_loss", correction, Z, Z.size(0) - int(n_users))
+    return _SoftmaxLoss.apply(Z, u.reshape(-1), cand, int(n_users), Z.size(0) - int(n_users), temperature, corr)
 
 
 class _SharedSoftmaxLoss(torch.autograd.Function):
@@ -1976,7 +2011,8 @@ class _SharedSoftmaxLoss(torch.autograd.Function):
     layer that produced Z takes its ordinary backward prologue."""
 
     @staticmethod
-    def forward(ctx, Z, u, pos, pool, hist_ptr, hist_items, n_users: int, n_items: int, temperature: float):
+    def forward(ctx, Z, u, pos, pool, hist_ptr, hist_items, n_users: int, n_items: int, temperature: float,
+                corr=None):
         lib = _lib.load()
         # Z straight from a GATLayer: a hand-off an earlier consumer left on that node is stale
         # for the gradient this loss returns -- dropped in backward, never made here
@@ -1992,20 +2028,31 @@ class _SharedSoftmaxLoss(torch.autograd.Function):
             _check_dev("history ptr", hist_ptr, torch.int64, Z.device)
             _check_dev("history items", hist_items, torch.int32, Z.device)
         _BadIndex.raise_pending()
-        ws, _ = _lib.workspace(lib.ppgat_shs_workspace_bytes, n_rows, S, P, C, device=Z.device)
+        ws, _ = _lib.workspace(lib.ppgat_shs_workspace_bytes if corr is None else
+                               lib.ppgat_shs_corrected_workspace_bytes, n_rows, S, P, C, device=Z.device)
         loss = torch.empty(1, dtype=torch.float32, device=Z.device)
         lse = torch.empty(max(S, 1), dtype=torch.float32, device=Z.device)
         c0 = torch.empty(max(S, 1), dtype=torch.float32, device=Z.device)
         bad = torch.empty(2, dtype=torch.int32, device=Z.device)
-        _lib.check(lib.ppgat_shs_fwd(Z.data_ptr(), n_rows, n_users, n_items, C, u.data_ptr(), pos.data_ptr(), S,
-                                     pool.data_ptr(), P, _lib.ptr(hist_ptr), _lib.ptr(hist_items), temperature,
-                                     loss.data_ptr(), lse.data_ptr(), c0.data_ptr(), bad.data_ptr(), ws.data_ptr(),
-                                     ws.numel(), _lib.stream_handle(Z.device)), "shs_fwd")
+        if corr is None:
+            _lib.check(lib.ppgat_shs_fwd(Z.data_ptr(), n_rows, n_users, n_items, C, u.data_ptr(), pos.data_ptr(), S,
+                                         pool.data_ptr(), P, _lib.ptr(hist_ptr), _lib.ptr(hist_items), temperature,
+                                         loss.data_ptr(), lse.data_ptr(), c0.data_ptr(), bad.data_ptr(),
+                                         ws.data_ptr(), ws.numel(), _lib.stream_handle(Z.device)), "shs_fwd")
+        else:
+            _track_correction("shared_softmax_loss", corr[pool.clamp(0, n_items - 1)])
+            _lib.check(lib.ppgat_shs_fwd_corrected(Z.data_ptr(), n_rows, n_users, n_items, C, u.data_ptr(),
+                                                   pos.data_ptr(), S, pool.data_ptr(), P, _lib.ptr(hist_ptr),
+                                                   _lib.ptr(hist_items), corr.data_ptr(), temperature,
+                                                   loss.data_ptr(), lse.data_ptr(), c0.data_ptr(), bad.data_ptr(),
+                                                   ws.data_ptr(), ws.numel(), _lib.stream_handle(Z.device)),
+                       "shs_fwd_corrected")
         _BadIndex.track(bad[1:], (ValueError, "shared_softmax_loss: pool must be strictly ascending "
                                               "({} entries not above their predecessor)"))
         _BadIndex.track(bad[:1], (IndexError, "shared_softmax_loss: {} of u/pos/pool out of range"))
         ctx.save_for_backward(Z, u, pos, pool, lse, c0)
-        ctx.ws = ws  # the mask words the forward left: the backward reads them
+        ctx.ws = ws  # the mask words (and gathered corrections) the forward left: the backward reads them
+        ctx.corrected = corr is not None
         ctx.meta = (n_rows, n_users, n_items, C, S, P, temperature)
         return loss.view(())
 
@@ -2019,12 +2066,12 @@ class _SharedSoftmaxLoss(torch.autograd.Function):
         prod, ctx.producer = ctx.producer, None
         if prod is not None:
             prod.pro_result = None
-        _lib.check(lib.ppgat_shs_bwd(Z.data_ptr(), n_rows, n_users, n_items, C, u.data_ptr(), pos.data_ptr(), S,
-                                     pool.data_ptr(), P, temperature, lse.data_ptr(), c0.data_ptr(), gl.data_ptr(),
-                                     dZ.data_ptr(), ctx.ws.data_ptr(), ctx.ws.numel(),
-                                     _lib.stream_handle(Z.device)), "shs_bwd")
+        entry = lib.ppgat_shs_bwd_corrected if ctx.corrected else lib.ppgat_shs_bwd
+        _lib.check(entry(Z.data_ptr(), n_rows, n_users, n_items, C, u.data_ptr(), pos.data_ptr(), S, pool.data_ptr(), P,
+                         temperature, lse.data_ptr(), c0.data_ptr(), gl.data_ptr(), dZ.data_ptr(), ctx.ws.data_ptr(),
+                         ctx.ws.numel(), _lib.stream_handle(Z.device)), entry.__name__[6:])
         ctx.ws = None
-        return dZ, None, None, None, None, None, None, None, None
+        return (dZ,) + (None,) * (9 if ctx.corrected else 8)  # (one per input of this apply)
 
 
 def shared_softmax_loss(Z: torch.Tensor, n_users: int, u, pos, pool, temperature: float = 1.0,
@@ -2034,7 +2081,17 @@ def shared_softmax_loss(Z: torch.Tensor, n_users: int, u, pos, pool, temperature
     ``BPRSampler.sample_pool``); ``mean_t(log(exp(s0) + sum_j exp(s[t, j])) - s0)`` over the pool
     items that are neither the sample's positive nor in its user's ``history`` (a ``BPRSampler``
     or its ``(ptr, items)`` pair; None: only the positive is masked).  The scores are a
-    matrix-core product that is never written; deterministic backward (no float atomics)."""
+    matrix-core product that is never written; deterministic backward (no float atomics).
+    A pool that was not drawn uniformly takes ``shared_softmax_loss_corrected``."""
+    return shared_softmax_loss_corrected(Z, n_users, u, pos, pool, temperature, history=history, correction=None)
+
+
+def shared_softmax_loss_corrected(Z: torch.Tensor, n_users: int, u, pos, pool, temperature: float = 1.0,
+                                  history=None, correction=None) -> torch.Tensor:
+    """``shared_softmax_loss`` with a logQ term: ``correction`` (fp32 [n_items], e.g.
+    ``BPRSampler.pool_correction()``) is subtracted from the logit of every pool entry,
+    ``s[t, j] -= correction[pool[j]]``, never from the positive's own logit; it takes no gradient,
+    and the pool's terms must not be -inf or NaN.  ``None``: the uncorrected entries and code path."""
     for name, t in (("u", u), ("pos", pos), ("pool", pool)):
         if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 1:
             raise ValueError(f"shared_softmax_loss: {name} must be a 1-D int64 tensor")
@@ -2053,8 +2110,12 @@ def shared_softmax_loss(Z: torch.Tensor, n_users: int, u, pos, pool, temperature
         hist_ptr, hist_items = (history.ptr, history.items) if hasattr(history, "ptr") else history
         if hist_ptr.numel() != int(n_users) + 1:
             raise ValueError("shared_softmax_loss: history ptr must have n_users + 1 entries")
+    if correction is None:
+        return _SharedSoftmaxLoss.apply(Z, u, pos, pool, hist_ptr, hist_items, int(n_users),
+                                        Z.size(0) - int(n_users), temperature)
+    corr = _check_correction("shared_softmax_loss", correction, Z, Z.size(0) - int(n_users))
     return _SharedSoftmaxLoss.apply(Z, u, pos, pool, hist_ptr, hist_items, int(n_users), Z.size(0) - int(n_users),
-                                    temperature)
+                                    temperature, corr)
 
 
 def bpr_loss_mapped(Z: torch.Tensor, n_users: int, n_items: int, row_map: torch.Tensor, u, i, j,

@@ -167,15 +167,18 @@ def bpr_loss(Z: torch.Tensor, n_users: int, u, i, j, loss: str = "bpr", prepared
     return hip_ops.bpr_loss(Z, n_users, u, i, j, loss, prepared=prepared)
 
 
-def softmax_loss(Z: torch.Tensor, n_users: int, u, cand, temperature: float = 1.0) -> torch.Tensor:
+def softmax_loss(Z: torch.Tensor, n_users: int, u, cand, temperature: float = 1.0, correction=None) -> torch.Tensor:
     """Sampled-softmax loss of the positive ``cand[:, 0]`` against the negatives ``cand[:, 1:]``,
-    fused on the device (ppgat_ssm_fwd / ppgat_ssm_bwd)."""
-    return hip_ops.softmax_loss(Z, n_users, u, cand, temperature)
+    fused on the device (ppgat_ssm_fwd / ppgat_ssm_bwd); ``correction``: the negatives' logQ table."""
+    return hip_ops.softmax_loss(Z, n_users, u, cand, temperature, correction=correction)
 
 
 def shared_softmax_loss(Z: torch.Tensor, n_users: int, u, pos, pool, temperature: float = 1.0,
-                        history=None) -> torch.Tensor:
+                        history=None, correction=None) -> torch.Tensor:
     """Softmax loss of the positives ``pos`` against one ``pool`` of item ids shared by every sample,
     the sample's positive and its user's ``history`` masked out, fused on the device
-    (ppgat_shs_fwd / ppgat_shs_bwd)."""
-    return hip_ops.shared_softmax_loss(Z, n_users, u, pos, pool, temperature, history=history)
+    (ppgat_shs_fwd / ppgat_shs_bwd); ``correction``: the pool's logQ table."""
+    if correction is None:
+        return hip_ops.shared_softmax_loss(Z, n_users, u, pos, pool, temperature, history=history)
+    return hip_ops.shared_softmax_loss_corrected(Z, n_users, u, pos, pool, temperature, history=history,
+                                                 correction=correction)

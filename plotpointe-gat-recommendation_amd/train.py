@@ -99,6 +99,10 @@ class Config:
     model_family: str = "gat_pyg"
     share_weights: bool = False  # gatv2_pyg: lin_r is lin_l
     edge_features: str = "none"  # gat_pyg: "rating" feeds (r - 1) / 4 per edge to GATConv(edge_dim=1)
+    negative_sampling: str = "uniform"  # "popularity": negatives drawn in proportion to (train count)^power
+    popularity_power: float = 0.75
+    logq: str = "auto"           # loss "softmax": subtract log(expected count) from the sampled logits;
+    #                              "auto" = on exactly when negative_sampling is "popularity"
     negatives: int = 16          # loss "softmax": sampled negatives per positive (a convention, not tuned)
     temperature: float = 1.0     # loss "softmax": the logits are <u, i> / temperature
 
@@ -208,6 +212,37 @@ def check_softmax_loss(args):
         raise ValueError("--temperature must be finite and > 0")
 
 
+def check_negative_sampling(args) -> bool:
+    """--negative-sampling / --popularity-power / --logq -> whether the logQ correction is on.
+    Popularity sampling and the correction are the GAT families' on one GPU (refused like --loss
+    softmax elsewhere); the correction exists for --loss softmax only, and it needs the sampling
+    distribution, so --logq on needs --negative-sampling popularity; popularity-weighted BPR/BCE
+    negatives come from the device sampler (--fast-sampler)."""
+    pop = args.negative_sampling == "popularity"
+    if not pop and args.logq != "on":
+        return False
+    if args.model_family == "lightgcn":
+        raise NotImplementedError("--negative-sampling popularity / --logq on with --model-family lightgcn is not "
+                                  "implemented: the LightGCN trainer keeps its uniform mini-batch negatives")
+    if args.world_size > 1:
+        raise NotImplementedError(f"--negative-sampling popularity / --logq on with --world-size {args.world_size} is "
+                                  "not implemented: the sharded trainers draw uniform negatives (--world-size 1)")
+    if not pop:
+        raise ValueError("--logq on needs --negative-sampling popularity: the correction is the log of the sampling "
+                         "distribution, which the uniform samplers do not carry")
+    if not (args.popularity_power >= 0 and args.popularity_power != float("inf")):
+        raise ValueError("--popularity-power must be finite and >= 0")
+    if args.loss != "softmax":
+        if args.logq == "on":
+            raise ValueError(f"--logq on with --loss {args.loss}: the correction is the sampled softmax's; no "
+                             "correction exists for the pairwise losses")
+        if not args.fast_sampler:
+            raise ValueError(f"--negative-sampling popularity with --loss {args.loss} needs --fast-sampler: the "
+                             "weighted negatives are drawn by the device sampler")
+        return False
+    return args.logq != "off"
+
+
 def build_model(cfg: Config, n_users: int, n_items: int, feat_dim: int):
     if cfg.model_family == "gat_pyg":
         return model_mod.PyGGAT(n_users, n_items, item_feat_dim=feat_dim, hidden=cfg.hidden_dim, layers=cfg.layers,
@@ -231,20 +266,22 @@ def epoch_step(model, opt, item_feats, edge_index, n_users: int, u, i, j, loss: 
     on a side stream before the forward (hip_ops.bpr_prepare; measured no faster at config 2,
     DESIGN.md section 4).  ``softmax`` = (cand [S, M + 1], temperature): the sampled-softmax loss of
     those candidates (column 0 the positive of u) instead; ``loss``, i and j are then not used.
+    Either tuple may end with a logQ correction table (fp32 [n_items]) for its loss.
     ``shared`` = (pool [P], history, temperature): the shared-negatives softmax loss of the positives i
     against that pool, ``history`` (the device sampler) excluded; ``loss`` and j are then not used."""
     if shared is not None:
-        pool, history, temperature = shared
+        pool, history, temperature, *corr = shared
         Z = model(item_feats, edge_index) if edge_attr is None else model(item_feats, edge_index, edge_attr)
-        lo = model_mod.shared_softmax_loss(Z, n_users, u, i, pool, temperature, history=history)
+        lo = model_mod.shared_softmax_loss(Z, n_users, u, i, pool, temperature, history=history,
+                                           correction=corr[0] if corr else None)
         opt.zero_grad()
         lo.backward()
         opt.step()
         return lo
     if softmax is not None:
-        cand, temperature = softmax
+        cand, temperature, *corr = softmax
         Z = model(item_feats, edge_index) if edge_attr is None else model(item_feats, edge_index, edge_attr)
-        lo = model_mod.softmax_loss(Z, n_users, u, cand, temperature)
+        lo = model_mod.softmax_loss(Z, n_users, u, cand, temperature, correction=corr[0] if corr else None)
         opt.zero_grad()
         lo.backward()
         opt.step()
@@ -483,6 +520,13 @@ def build_parser():
                          "0 = off")
     ap.add_argument("--temperature", type=float, default=1.0,
                     help="--loss softmax: logits are <user, item> / temperature")
+    ap.add_argument("--negative-sampling", choices=["uniform", "popularity"], default="uniform",
+                    help="popularity: negatives (BPR/BCE j with --fast-sampler, the softmax candidates, the shared "
+                         "pool) drawn in proportion to (train count)^--popularity-power (GAT families, one GPU)")
+    ap.add_argument("--popularity-power", type=float, default=0.75)
+    ap.add_argument("--logq", choices=["auto", "on", "off"], default="auto",
+                    help="--loss softmax: subtract the log of each sampled negative's expected count from its logit; "
+                         "auto = on exactly when --negative-sampling popularity")
     ap.add_argument("--deterministic", action="store_true")
     ap.add_argument("--structured-logs", action="store_true")
     ap.add_argument("--fast-eval", action="store_true", help="vectorised negative sampling (same distribution)")
@@ -511,6 +555,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     check_edge_features(args)
     check_softmax_loss(args)
+    logq = check_negative_sampling(args)
     if args.recommend_out and args.world_size > 1:
         raise NotImplementedError("--recommend-out runs on one GPU (--world-size 1): the lists are made from the "
                                   "whole user and item tables")
@@ -529,7 +574,8 @@ def main(argv=None):
                  attn_dropout=args.attn_dropout, epochs=args.epochs, samples_per_epoch=args.samples_per_epoch,
                  seed=args.seed, eval_neg_k=args.eval_neg_k, item_features=args.item_features, loss=args.loss,
                  model_family=args.model_family, share_weights=args.share_weights,
-                 edge_features=args.edge_features, negatives=args.negatives, temperature=args.temperature)
+                 edge_features=args.edge_features, negatives=args.negatives, temperature=args.temperature,
+                 negative_sampling=args.negative_sampling, popularity_power=args.popularity_power, logq=args.logq)
     if args.lr is not None:
         cfg.lr = args.lr
     if args.l2 is not None:
@@ -596,7 +642,11 @@ def main(argv=None):
     dev_sampler = None
     if args.fast_sampler or args.device_eval or full or cfg.loss == "softmax":
         ptr, flat = user_csr(tr, n_users)
-        dev_sampler = sampler_mod.BPRSampler(ptr, flat, n_items, device=device)
+        weights = None
+        if cfg.negative_sampling == "popularity":  # from the train interactions
+            weights = sampler_mod.BPRSampler.popularity_weights(ptr, flat, n_items, cfg.popularity_power)
+        dev_sampler = sampler_mod.BPRSampler(ptr, flat, n_items, device=device, item_weights=weights)
+    ssm_corr = dev_sampler.correction(cfg.negatives) if logq and args.shared_negatives == 0 else None
     for epoch in range(1, cfg.epochs + 1):
         model.train()
         if args.fast_sampler:
@@ -612,8 +662,12 @@ def main(argv=None):
             if cfg.loss == "softmax" and args.shared_negatives > 0:  # one pool for the epoch's positives
                 shared = (dev_sampler.sample_pool(args.shared_negatives, cfg.seed + epoch), dev_sampler,
                           cfg.temperature)
+                if logq:  # the pool's inclusion probabilities depend on how many draws it took
+                    shared += (dev_sampler.pool_correction(),)
             elif cfg.loss == "softmax":  # the negatives always come from the device sampler
-                softmax = (dev_sampler.eval_candidates(u, i, cfg.negatives, seed=cfg.seed + epoch), cfg.temperature)
+                softmax = (dev_sampler.train_candidates(u, i, cfg.negatives, seed=cfg.seed + epoch), cfg.temperature)
+                if logq:
+                    softmax += (ssm_corr,)
             loss_val = float(epoch_step(model, opt, item_feats, edge_index, n_users, u, i, j, cfg.loss,
                                         edge_attr=edge_attr, softmax=softmax, shared=shared).item())
         else:
@@ -667,6 +721,9 @@ def main(argv=None):
                          f"excluded, temperature {cfg.temperature}; --negatives unused)")
     elif cfg.loss == "softmax":
         out["notes"] += f" ({cfg.negatives} sampled negatives per positive, temperature {cfg.temperature})"
+    if cfg.negative_sampling == "popularity":
+        out["notes"] += (f"; negatives drawn in proportion to (train count)^{cfg.popularity_power}, logQ correction "
+                         f"{'on' if logq else 'off'}")
     if full:
         out["config"] = {**cfg.__dict__, "eval_mode": "full"}
         out["notes"] += "; " + FULL_EVAL_NOTE
