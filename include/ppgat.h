@@ -640,6 +640,43 @@ int ppgat_dynatt_bwd(const ppgat_schedule* src_sched, const ppgat_schedule* dst_
                      float dropout_p, const uint64_t* seed_used, float* grad_x_l, float* grad_x_r, float* grad_att,
                      float* grad_bias, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- attention weights and the most-attended neighbours ---------------------------------
+ * Replaces: the alpha of torch_geometric's return_attention_weights=True (GATConv, GATv2Conv),
+ *   and a per-destination sort of it.  alpha [E, H] is the forward's softmax weight BEFORE the
+ *   dropout mask, recomputed per edge from the forward's own final state m and inv_l [N, H]:
+ *     PyG mode     alpha = exp(e - m_i) * inv_l_i,  e = leaky_relu((s_src[j] + s_dst[i]) [+ edge_term[k]])
+ *     custom mode  alpha = exp(clamp(leaky_relu(z), -10, 10)) * inv_l_i     (no max subtraction)
+ *     GATv2        e = att_h . leaky_relu(x_l[j] + x_r[i]),  alpha = exp(e - m_i) * inv_l_i
+ *   with the arithmetic of the forward kernels, so that given the s_src / s_dst (x_l / x_r) the
+ *   state was computed from, e - m <= 0 for every edge and a destination's largest weight is
+ *   inv_l_i bit for bit.  There is no second reduction: hub pieces need no merge, no workspace.
+ * order = 0: alpha[slot] (CSR slot order); order = 1: alpha[csr_eid[slot]] (the caller's
+ *   edge_index column order; csr_eid required).  Every element of alpha is written exactly once.
+ * ppgat_attention: dst_sched, col, csr_eid of the CSR by destination; s_src [>= max col + 1, H];
+ *   s_dst, m, inv_l [n_nodes, H]; edge_term [E, H] in CSR slot order or NULL; heads <= 8 in
+ *   either mode (the forward's custom mode is heads == 1; this entry reads whatever state it is
+ *   given).
+ * ppgat_dynatt_attention: the (heads, channels) of ppgat_dynatt_supported, others
+ *   PPGAT_ERR_UNSUPPORTED before any device work; x_l, x_r [n_nodes, H, C], att [H, C].
+ * ppgat_attention_topk: per destination i (one wave each, walking the whole row), the k (1..32)
+ *   in-edges with the largest v = (sum_h val[slot, h]) * (1 / heads), val [E, H] in CSR slot
+ *   order, ranked exactly under (v descending, original edge id ascending; NaN ranks as -inf):
+ *   out_eid [N, k] the original edge ids (csr_eid; -1 pads), out_val [N, k] their v (0 in the
+ *   pads), out_cnt [N] = min(k, in-degree).  It ranks whatever [E, H] array it is given.
+ * All three validate on the host first (PPGAT_ERR_INVALID / PPGAT_ERR_UNSUPPORTED with nothing
+ * launched), use no float atomics (two calls give the same bits) and never synchronise. */
+int ppgat_attention(const ppgat_schedule* dst_sched, const int32_t* col, const int32_t* csr_eid,
+                    const float* edge_term, int64_t n_nodes, int64_t n_edges, int heads, const float* s_src,
+                    const float* s_dst, const float* m, const float* inv_l, int mode, float negative_slope,
+                    int order, float* alpha, void* stream);
+int ppgat_dynatt_attention(const ppgat_schedule* dst_sched, const int32_t* col, const int32_t* csr_eid,
+                           int64_t n_nodes, int64_t n_edges, int heads, int channels, const float* x_l,
+                           const float* x_r, const float* att, const float* m, const float* inv_l,
+                           float negative_slope, int order, float* alpha, void* stream);
+int ppgat_attention_topk(const int32_t* rowptr, const int32_t* csr_eid, const float* val, int64_t n_nodes,
+                         int64_t n_edges, int heads, int k, int32_t* out_eid, float* out_val, int32_t* out_cnt,
+                         void* stream);
+
 /* ---- sampled-evaluation candidates ---------------------------------------------------
  * Replaces: the candidate draw of eval_sampled, scripts/train_gat_pyg.py:157-167 (a Python
  *   loop over ~192k users: np.random.randint(0, n_items) redrawn while the item is in the

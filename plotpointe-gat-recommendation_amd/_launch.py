@@ -168,6 +168,29 @@ def dynatt_bwd(g, xl, xr, att, m, inv_l, grad_out, heads: int, channels: int, sl
           "gatv2_bwd")
 
 
+# attention weights from a forward's final state (``order`` 0: CSR slot order, 1: edge_index
+# column order) and the per-destination selection; ``g``: a hip_ops.CSRGraph
+def attention(g, s_src, s_dst, m, inv_l, heads: int, mode: int, slope, order: int, alpha, edge_term=None):
+    E = g.n_edges
+    check(load().ppgat_attention(_sched(g.fwd_sched), *edge_ptrs(E, g.col, g.csr_eid, edge_term), g.n_nodes, E,
+                                 heads, ptr(s_src), ptr(s_dst), ptr(m), ptr(inv_l), mode, float(slope), order,
+                                 ptr(alpha), stream_handle(alpha.device)), "attention")
+
+
+def dynatt_attention(g, xl, xr, att, m, inv_l, heads: int, channels: int, slope, order: int, alpha):
+    E = g.n_edges
+    check(load().ppgat_dynatt_attention(_sched(g.fwd_sched), *edge_ptrs(E, g.col, g.csr_eid), g.n_nodes, E, heads,
+                                        channels, ptr(xl), ptr(xr), ptr(att), ptr(m), ptr(inv_l), float(slope),
+                                        order, ptr(alpha), stream_handle(alpha.device)), "gatv2_attention")
+
+
+def attention_topk(g, val, heads: int, k: int, out_eid, out_val, out_cnt):
+    E = g.n_edges
+    check(load().ppgat_attention_topk(ptr(g.rowptr), *edge_ptrs(E, g.csr_eid, val), g.n_nodes, E, heads, k,
+                                      ptr(out_eid), ptr(out_val), ptr(out_cnt), stream_handle(out_eid.device)),
+          "attention_topk")
+
+
 # the aggregate-then-transform layer (ppgat_xgat_*); ``v``: a hip_ops.XViews
 def xgat_weights(W, a_s, a_d, H: int, C: int, A=None, Wt=None, Wg=None):
     """Whichever of A [2, H, K] (needs a_s, a_d), Wt [H * K, C] and Wg [C, H * K] are given."""

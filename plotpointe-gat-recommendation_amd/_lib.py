@@ -129,6 +129,11 @@ SIGNATURES = {
                                  c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "ppgat_dynatt_bwd": (c_int, [SP, SP, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp,
                                  c_vp, c_vp, c_f, c_f, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "ppgat_attention": (c_int, [SP, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_f, c_int,
+                                c_vp, c_vp]),
+    "ppgat_dynatt_attention": (c_int, [SP, c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_f,
+                                       c_int, c_vp, c_vp]),
+    "ppgat_attention_topk": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     "ppgat_edge_attr_permute": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_vp]),
     "ppgat_edge_terms": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp]),
     "ppgat_edge_fwd": (c_int, [SP, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_f,

@@ -23,6 +23,14 @@ edge kernels, and a backward that folds the attention terms into the projection 
 multi-head layers wider than their input (config 5) run aggregate-then-transform
 (``hip_ops.GATLayerX``: x_j gathered once per edge, one transform GEMM).  Dropout on alpha is the counter-hash mask of
 include/ppgat.h, drawn fresh per training forward from torch's CPU generator.
+
+``forward(..., return_attention_weights=True)`` returns PyG's tuple ``(out, (edge_index, alpha))``
+with alpha [E, H] fp32 in edge_index column order, detached.  alpha is the softmax weight BEFORE
+the dropout mask, in train mode too: each destination's weights sum to 1 and the result is
+deterministic.  (PyG >= 2.3 returns the weights after dropout in train mode; in eval mode the two
+agree.)  ``out`` comes from the same call as without the flag; alpha from a second, no-grad
+forward over the unfused primitives (``layer.attention``), so the flag costs about one more
+forward.
 """
 from __future__ import annotations
 
@@ -31,8 +39,8 @@ import math
 import torch
 
 from . import _lib
-from .hip_ops import (EDGE_MAX_DIM, check_edge_attr, gat_layer, gatv2_aggregate, gatv2_supported, graph_cache,
-                      join_rows, linear)
+from .hip_ops import (EDGE_MAX_DIM, check_edge_attr, gat_layer, gat_layer_attention, gatv2_aggregate,
+                      gatv2_layer_attention, gatv2_supported, graph_cache, join_rows, linear)
 
 
 def _dropout_seed() -> int:
@@ -126,27 +134,47 @@ class GATConv(torch.nn.Module):
         v = (w * self.att_edge.view(self.heads, self.out_channels, 1)).sum(1)
         return {"edge_v": v, "edge_attr": edge_attr}
 
+    def attention(self, x: torch.Tensor, edge_index: torch.Tensor, edge_attr=None, x_items=None,
+                  order: str = "edge") -> torch.Tensor:
+        """alpha [E, H] of forward(x, edge_index, edge_attr) -- of forward_segments with ``x_items`` --
+        before the dropout mask, whatever the training flag: fp32, no gradient, row k for column k of
+        edge_index (``order="slot"``: CSR slot order, what hip_ops.attention_topk reads).  A forward of
+        its own (hip_ops.gat_layer_attention)."""
+        n = x.size(0) + (x_items.size(0) if x_items is not None else 0)
+        graph = graph_cache.get(edge_index, n)
+        with torch.no_grad():
+            ea = self._edge_args(edge_attr, graph.n_edges, x.device)
+        return gat_layer_attention(x, self.lin.weight, self.att_src, self.att_dst, graph, self.heads,
+                                   self.out_channels, _lib.MODE_PYG, float(self.negative_slope), x_items=x_items,
+                                   order=order, **ea)
+
     def forward(self, x: torch.Tensor, edge_index: torch.Tensor, edge_attr=None,
                 return_attention_weights=None) -> torch.Tensor:
-        if return_attention_weights:
-            raise NotImplementedError("return_attention_weights not implemented")
+        """``return_attention_weights=True``: ``(out, (edge_index, alpha))``, alpha [E, H] before the
+        dropout mask (see the module docstring); costs a second forward."""
         graph = graph_cache.get(edge_index, x.size(0))
         p = float(self.dropout) if self.training else 0.0
         seed = _dropout_seed() if p > 0 else 0
-        return gat_layer(x, self.lin.weight, self.att_src, self.att_dst, self.bias, graph, self.heads,
-                         self.out_channels, _lib.MODE_PYG, float(self.negative_slope), p, seed,
-                         **self._edge_args(edge_attr, graph.n_edges, x.device))
+        out = gat_layer(x, self.lin.weight, self.att_src, self.att_dst, self.bias, graph, self.heads,
+                        self.out_channels, _lib.MODE_PYG, float(self.negative_slope), p, seed,
+                        **self._edge_args(edge_attr, graph.n_edges, x.device))
+        if return_attention_weights:
+            return out, (edge_index, self.attention(x, edge_index, edge_attr))
+        return out
 
     def forward_segments(self, x: torch.Tensor, x_items: torch.Tensor, edge_index: torch.Tensor,
-                         edge_attr=None) -> torch.Tensor:
+                         edge_attr=None, return_attention_weights=None) -> torch.Tensor:
         """forward(cat(x, x_items), edge_index, edge_attr) without materialising the concatenation
         (the model's node features, train_gat_pyg.py:79-82)."""
         graph = graph_cache.get(edge_index, x.size(0) + x_items.size(0))
         p = float(self.dropout) if self.training else 0.0
         seed = _dropout_seed() if p > 0 else 0
-        return gat_layer(x, self.lin.weight, self.att_src, self.att_dst, self.bias, graph, self.heads,
-                         self.out_channels, _lib.MODE_PYG, float(self.negative_slope), p, seed, x_items=x_items,
-                         **self._edge_args(edge_attr, graph.n_edges, x.device))
+        out = gat_layer(x, self.lin.weight, self.att_src, self.att_dst, self.bias, graph, self.heads,
+                        self.out_channels, _lib.MODE_PYG, float(self.negative_slope), p, seed, x_items=x_items,
+                        **self._edge_args(edge_attr, graph.n_edges, x.device))
+        if return_attention_weights:
+            return out, (edge_index, self.attention(x, edge_index, edge_attr, x_items=x_items))
+        return out
 
     def __repr__(self):
         return (f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, heads={self.heads}, "
@@ -199,24 +227,40 @@ class GATv2Conv(torch.nn.Module):
         if self.bias is not None:
             torch.nn.init.zeros_(self.bias)
 
-    def _aggregate(self, x: torch.Tensor, edge_index: torch.Tensor) -> torch.Tensor:
+    def _aggregate(self, x: torch.Tensor, edge_index: torch.Tensor, want_alpha=None):
         graph = graph_cache.get(edge_index, x.size(0))
         p = float(self.dropout) if self.training else 0.0
         seed = _dropout_seed() if p > 0 else 0
         xl = linear(x, self.lin_l.weight, self.lin_l.bias)
         xr = xl if self.share_weights else linear(x, self.lin_r.weight, self.lin_r.bias)
-        return gatv2_aggregate(xl, xr, self.att, self.bias, graph, self.heads, self.out_channels,
-                               float(self.negative_slope), p, seed)
+        out = gatv2_aggregate(xl, xr, self.att, self.bias, graph, self.heads, self.out_channels,
+                              float(self.negative_slope), p, seed)
+        if want_alpha:  # from the projections at hand: a second aggregate, no second projection
+            return out, (edge_index, gatv2_layer_attention(xl, xr, self.att, graph, self.heads, self.out_channels,
+                                                           float(self.negative_slope)))
+        return out
+
+    def attention(self, x: torch.Tensor, edge_index: torch.Tensor, order: str = "edge") -> torch.Tensor:
+        """alpha [E, H] of forward(x, edge_index) before the dropout mask, whatever the training flag:
+        fp32, no gradient, row k for column k of edge_index (``order="slot"``: CSR slot order).  A
+        forward of its own: ``linear`` and hip_ops.gatv2_layer_attention."""
+        graph = graph_cache.get(edge_index, x.size(0))
+        with torch.no_grad():
+            xl = linear(x, self.lin_l.weight, self.lin_l.bias)
+            xr = xl if self.share_weights else linear(x, self.lin_r.weight, self.lin_r.bias)
+        return gatv2_layer_attention(xl, xr, self.att, graph, self.heads, self.out_channels,
+                                     float(self.negative_slope), order=order)
 
     def forward(self, x: torch.Tensor, edge_index: torch.Tensor, return_attention_weights=None) -> torch.Tensor:
-        if return_attention_weights:
-            raise NotImplementedError("return_attention_weights not implemented")
-        return self._aggregate(x, edge_index)
+        """``return_attention_weights=True``: ``(out, (edge_index, alpha))``, alpha [E, H] before the
+        dropout mask (see the module docstring); costs a second aggregate."""
+        return self._aggregate(x, edge_index, return_attention_weights)
 
-    def forward_segments(self, x: torch.Tensor, x_items: torch.Tensor, edge_index: torch.Tensor) -> torch.Tensor:
+    def forward_segments(self, x: torch.Tensor, x_items: torch.Tensor, edge_index: torch.Tensor,
+                         return_attention_weights=None) -> torch.Tensor:
         """forward(cat(x, x_items), edge_index); the two blocks are joined without a copy when they
         lie back to back (the model's node table), else concatenated."""
-        return self._aggregate(join_rows(x, x_items), edge_index)
+        return self._aggregate(join_rows(x, x_items), edge_index, return_attention_weights)
 
     def __repr__(self):
         return (f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, heads={self.heads}, "
@@ -241,17 +285,36 @@ class SimpleGATLayer(torch.nn.Module):
         self.drop = torch.nn.Dropout(attn_dropout)
         self.out_dim = out_dim
 
-    def forward(self, x: torch.Tensor, edge_index: torch.Tensor) -> torch.Tensor:
+    def attention(self, x: torch.Tensor, edge_index: torch.Tensor, x_items=None, order: str = "edge") -> torch.Tensor:
+        """alpha [E, 1] of forward(x, edge_index) -- of forward_segments with ``x_items`` -- before the
+        dropout mask, whatever the training flag: exp(clamp(leaky_relu(z), -10, 10)) / (sum + 1e-9),
+        fp32, no gradient, row k for column k of edge_index (``order="slot"``: CSR slot order).  A
+        forward of its own (hip_ops.gat_layer_attention)."""
+        n = x.size(0) + (x_items.size(0) if x_items is not None else 0)
+        graph = graph_cache.get(edge_index, n)
+        return gat_layer_attention(x, self.lin.weight, self.a_src, self.a_dst, graph, 1, self.out_dim,
+                                   _lib.MODE_CUSTOM, float(self.leaky.negative_slope), x_items=x_items, order=order)
+
+    def forward(self, x: torch.Tensor, edge_index: torch.Tensor, return_attention_weights=None) -> torch.Tensor:
+        """``return_attention_weights=True``: ``(out, (edge_index, alpha))``, alpha [E, 1] before the
+        dropout mask (see the module docstring); costs a second forward."""
         graph = graph_cache.get(edge_index, x.size(0))
         p = float(self.drop.p) if self.training else 0.0
         seed = _dropout_seed() if p > 0 else 0
-        return gat_layer(x, self.lin.weight, self.a_src, self.a_dst, None, graph, 1, self.out_dim, _lib.MODE_CUSTOM,
-                         float(self.leaky.negative_slope), p, seed)
+        out = gat_layer(x, self.lin.weight, self.a_src, self.a_dst, None, graph, 1, self.out_dim, _lib.MODE_CUSTOM,
+                        float(self.leaky.negative_slope), p, seed)
+        if return_attention_weights:
+            return out, (edge_index, self.attention(x, edge_index))
+        return out
 
-    def forward_segments(self, x: torch.Tensor, x_items: torch.Tensor, edge_index: torch.Tensor) -> torch.Tensor:
+    def forward_segments(self, x: torch.Tensor, x_items: torch.Tensor, edge_index: torch.Tensor,
+                         return_attention_weights=None) -> torch.Tensor:
         """forward(cat(x, x_items), edge_index) without materialising the concatenation."""
         graph = graph_cache.get(edge_index, x.size(0) + x_items.size(0))
         p = float(self.drop.p) if self.training else 0.0
         seed = _dropout_seed() if p > 0 else 0
-        return gat_layer(x, self.lin.weight, self.a_src, self.a_dst, None, graph, 1, self.out_dim, _lib.MODE_CUSTOM,
-                         float(self.leaky.negative_slope), p, seed, x_items=x_items)
+        out = gat_layer(x, self.lin.weight, self.a_src, self.a_dst, None, graph, 1, self.out_dim, _lib.MODE_CUSTOM,
+                        float(self.leaky.negative_slope), p, seed, x_items=x_items)
+        if return_attention_weights:
+            return out, (edge_index, self.attention(x, edge_index, x_items=x_items))
+        return out

@@ -1336,6 +1336,80 @@ int ppgat_dynatt_bwd(const ppgat_schedule* src_sched, const ppgat_schedule* dst_
   return PPGAT_OK;
 }
 
+// ---- attention weights, most-attended neighbours ---------------------------------------
+static int attention_check(const ppgat_schedule* s, const int32_t* col, const int32_t* csr_eid, int64_t n_nodes,
+                           int64_t n_edges, int order, const float* alpha, const char* who) {
+  if (n_nodes < 0 || n_edges < 0) return fail(PPGAT_ERR_INVALID, std::string(who) + ": bad sizes");
+  if (n_nodes >= (int64_t)1 << 31 || n_edges >= (int64_t)1 << 31)
+    return fail(PPGAT_ERR_UNSUPPORTED, std::string(who) + ": nodes and edges must be < 2^31");
+  if (order != 0 && order != 1)
+    return fail(PPGAT_ERR_INVALID, std::string(who) + ": order must be 0 (CSR slot) or 1 (edge_index column)");
+  if (int rc = check_sched(s, n_nodes, who)) return rc;
+  if (n_edges > 0 && (!col || !alpha)) return fail(PPGAT_ERR_INVALID, std::string(who) + ": null col or alpha");
+  if (n_edges > 0 && order == 1 && !csr_eid)
+    return fail(PPGAT_ERR_INVALID, std::string(who) + ": order 1 needs csr_eid");
+  return PPGAT_OK;
+}
+
+int ppgat_attention(const ppgat_schedule* dst_sched, const int32_t* col, const int32_t* csr_eid,
+                    const float* edge_term, int64_t n_nodes, int64_t n_edges, int heads, const float* s_src,
+                    const float* s_dst, const float* m, const float* inv_l, int mode, float negative_slope,
+                    int order, float* alpha, void* stream) {
+  if (heads < 1) return fail(PPGAT_ERR_INVALID, "attention: bad sizes");
+  if (heads > ppgat::kMaxHeads) return fail(PPGAT_ERR_UNSUPPORTED, "attention: heads > 8 not supported");
+  if (mode != PPGAT_MODE_PYG && mode != PPGAT_MODE_CUSTOM) return fail(PPGAT_ERR_INVALID, "attention: unknown mode");
+  if (int rc = attention_check(dst_sched, col, csr_eid, n_nodes, n_edges, order, alpha, "attention")) return rc;
+  if (n_edges > 0 && (!s_src || !s_dst || !m || !inv_l)) return fail(PPGAT_ERR_INVALID, "attention: null pointer");
+  if (n_edges == 0) return PPGAT_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = dynatt_check_edges(dst_sched, col, n_nodes, n_edges, "attention: index", st)) return rc;
+  if (order == 1)
+    if (int rc = debug_range(csr_eid, 4, n_edges, 0, n_edges, "attention: csr_eid", st)) return rc;
+  Timed t(PPGAT_K_FWD, st);
+  hipError_t e = ppgat::launch_attention(*dst_sched, col, csr_eid, heads, s_src, s_dst, m, inv_l, mode,
+                                         negative_slope, order == 1, alpha, edge_term, st);
+  if (e != hipSuccess) return hip_fail(e, "attention");
+  return PPGAT_OK;
+}
+
+int ppgat_dynatt_attention(const ppgat_schedule* dst_sched, const int32_t* col, const int32_t* csr_eid,
+                           int64_t n_nodes, int64_t n_edges, int heads, int channels, const float* x_l,
+                           const float* x_r, const float* att, const float* m, const float* inv_l,
+                           float negative_slope, int order, float* alpha, void* stream) {
+  if (int rc = dynatt_check(heads, channels, 0.f, "dynatt_attention")) return rc;
+  if (int rc = attention_check(dst_sched, col, csr_eid, n_nodes, n_edges, order, alpha, "dynatt_attention")) return rc;
+  if (n_edges > 0 && (!x_l || !x_r || !att || !m || !inv_l))
+    return fail(PPGAT_ERR_INVALID, "dynatt_attention: null pointer");
+  if (n_edges == 0) return PPGAT_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = dynatt_check_edges(dst_sched, col, n_nodes, n_edges, "dynatt_attention: index", st)) return rc;
+  if (order == 1)
+    if (int rc = debug_range(csr_eid, 4, n_edges, 0, n_edges, "dynatt_attention: csr_eid", st)) return rc;
+  Timed t(PPGAT_K_FWD, st);
+  hipError_t e = ppgat::gatv2_attention(*dst_sched, col, csr_eid, heads, channels, x_l, x_r, att, m, inv_l,
+                                        negative_slope, order == 1, alpha, st);
+  if (e != hipSuccess) return hip_fail(e, "dynatt_attention");
+  return PPGAT_OK;
+}
+
+int ppgat_attention_topk(const int32_t* rowptr, const int32_t* csr_eid, const float* val, int64_t n_nodes,
+                         int64_t n_edges, int heads, int k, int32_t* out_eid, float* out_val, int32_t* out_cnt,
+                         void* stream) {
+  if (k < 1 || k > 32) return fail(PPGAT_ERR_INVALID, "attention_topk: k must be in [1, 32]");
+  if (heads < 1 || n_nodes < 0 || n_edges < 0) return fail(PPGAT_ERR_INVALID, "attention_topk: bad sizes");
+  if (heads > ppgat::kMaxHeads) return fail(PPGAT_ERR_UNSUPPORTED, "attention_topk: heads > 8 not supported");
+  if (n_nodes >= (int64_t)1 << 31 || n_edges >= (int64_t)1 << 31)
+    return fail(PPGAT_ERR_UNSUPPORTED, "attention_topk: nodes and edges must be < 2^31");
+  if (n_nodes > 0 && (!rowptr || !out_eid || !out_val || !out_cnt))
+    return fail(PPGAT_ERR_INVALID, "attention_topk: null pointer");
+  if (n_edges > 0 && (!csr_eid || !val)) return fail(PPGAT_ERR_INVALID, "attention_topk: null csr_eid or val");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = debug_range(rowptr, 4, n_nodes + 1, 0, n_edges + 1, "attention_topk: rowptr", st)) return rc;
+  hipError_t e = ppgat::attention_topk(rowptr, csr_eid, val, n_nodes, heads, k, out_eid, out_val, out_cnt, st);
+  if (e != hipSuccess) return hip_fail(e, "attention_topk");
+  return PPGAT_OK;
+}
+
 int ppgat_eval_sample(const int64_t* user_ptr, const int32_t* items_sorted, const int64_t* users, const int64_t* pos,
                       int64_t n_eval, int64_t n_neg, int64_t n_items, uint64_t seed, int64_t* cands, int32_t* bad,
                       void* stream) {

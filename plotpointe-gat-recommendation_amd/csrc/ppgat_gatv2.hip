@@ -218,6 +218,73 @@ __global__ void __launch_bounds__(256) k_v2_fwd_merge(const int32_t* __restrict_
 }
 
 // ---------------------------------------------------------------------------
+// Attention weights (ppgat_dynatt_attention): alpha = exp(e_ij - m_i) inv_l_i per edge and head,
+// before the dropout mask, from the forward's final state.  x_l[j] is gathered per edge and the
+// logit formed exactly as k_v2_fwd forms it (x_l[j] + x_r[i], leaky, dot with att, the same
+// subgroup reduction), so e <= m and a destination's largest weight is inv_l bit for bit.  One
+// wave per item, a hub piece being just another item; after the reduction every lane of a
+// subgroup holds every head's logit, and lane h of the subgroup stores head h.
+// ---------------------------------------------------------------------------
+struct AttnArgs {
+  const float* xl;
+  const float* xr;
+  const float* att;
+  const float* m;
+  const float* invl;
+  float slope;
+  int scatter;  // alpha at eid[k] (the caller's edge order) instead of at slot k
+  float* alpha;
+};
+
+template <int H, int C>
+__global__ void __launch_bounds__(256) k_v2_attn(Items it, const int32_t* __restrict__ col,
+                                                 const int32_t* __restrict__ eid, AttnArgs a) {
+  using G = Geo<H, C>;
+  static_assert(H <= G::LPR, "one lane of a subgroup per head");
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t w = (int64_t)blockIdx.x * 4 + wv;
+  if (w >= it.n_items) return;  // wave-uniform
+  const int sg = lane / G::LPR, sl = lane % G::LPR;
+  const int64_t i = it.row[w];
+  const int rs = it.beg[w], re = it.end[w];
+  float4 xr[H], at[H];
+  float mi[H], il[H];
+#pragma unroll
+  for (int h = 0; h < H; ++h) {
+    xr[h] = ld4(a.xr + (i * H + h) * C + sl * 4);
+    at[h] = ld4(a.att + h * C + sl * 4);
+    mi[h] = a.m[i * H + h];
+    il[h] = a.invl[i * H + h];
+  }
+  for (int k0 = rs; k0 < re; k0 += G::EPW * G::U) {  // wave-uniform trip count
+    float4 v[G::U][H];
+    int64_t o[G::U];
+    bool ok[G::U];
+#pragma unroll
+    for (int u = 0; u < G::U; ++u) {
+      const int k = k0 + u * G::EPW + sg;
+      ok[u] = k < re;
+      const int64_t j = ok[u] ? col[k] : 0;
+      o[u] = ok[u] ? (a.scatter ? eid[k] : k) : 0;
+#pragma unroll
+      for (int h = 0; h < H; ++h) v[u][h] = ok[u] ? ld4(a.xl + (j * H + h) * C + sl * 4) : f4(0.f);
+    }
+#pragma unroll
+    for (int u = 0; u < G::U; ++u) {
+      float mine = 0.f;
+#pragma unroll
+      for (int h = 0; h < H; ++h) {
+        const float4 lr = leaky4(add4(v[u][h], xr[h]), a.slope);
+        const float e = group_reduce<Op::Sum, 1, G::LPR / 2>(dot4(at[h], lr));
+        const float al = expf(e - mi[h]) * il[h];
+        if (sl == h) mine = al;
+      }
+      if (ok[u] && sl < H) a.alpha[o[u] * H + sl] = mine;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // dbias: the block partial column sums of g in a fixed order (rows side by side within a block,
 // the block's waves in wave order, blocks by launch_col_reduce).
 // ---------------------------------------------------------------------------
@@ -539,6 +606,24 @@ hipError_t gatv2_fwd(const ppgat_schedule& sch, const int32_t* col, const int32_
   if (sch.n_items <= 0) return hipSuccess;
   const FwdArgs a{xl, xr, att, bias, slope, p, p > 0.f ? 1.f / (1.f - p) : 1.f, seed, out, m, invl, partial};
   PPGAT_V2_DISPATCH(H, C, (fwd_t<HH, CC>(sch, col, eid, a, st)));
+}
+
+namespace {
+template <int H, int C>
+hipError_t attn_t(const ppgat_schedule& sch, const int32_t* col, const int32_t* eid, const AttnArgs& a,
+                  hipStream_t st) {
+  hipLaunchKernelGGL((k_v2_attn<H, C>), dim3((unsigned)((sch.n_items + 3) / 4)), dim3(256), 0, st,
+                     items_of(sch, sch.n_items), col, eid, a);
+  return hipGetLastError();
+}
+}  // namespace
+
+hipError_t gatv2_attention(const ppgat_schedule& sch, const int32_t* col, const int32_t* eid, int H, int C,
+                           const float* xl, const float* xr, const float* att, const float* m, const float* invl,
+                           float slope, bool scatter, float* alpha, hipStream_t st) {
+  if (sch.n_items <= 0) return hipSuccess;
+  const AttnArgs a{xl, xr, att, m, invl, slope, scatter ? 1 : 0, alpha};
+  PPGAT_V2_DISPATCH(H, C, (attn_t<HH, CC>(sch, col, eid, a, st)));
 }
 
 hipError_t gatv2_bwd(const ppgat_schedule& src, const ppgat_schedule& dst, const int32_t* row, const int32_t* csc_eid,

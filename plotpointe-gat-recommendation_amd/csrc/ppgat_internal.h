@@ -193,6 +193,17 @@ hipError_t gatv2_bwd(const ppgat_schedule& src, const ppgat_schedule& dst, const
                      const float* invl, const float* g, float slope, float p, const uint64_t* seed, float* dxl,
                      float* dxr, float* datt, float* dbias, void* ws, hipStream_t st);
 
+// attention weights [E, H] from a forward's final state (ppgat_kernels.hip, ppgat_gatv2.hip;
+// scatter: at eid[slot] instead of at the slot) and the per-destination selection (ppgat_knn.hip)
+hipError_t launch_attention(const ppgat_schedule& sch, const int32_t* col, const int32_t* eid, int heads,
+                            const float* ss, const float* sd, const float* m, const float* invl, int mode,
+                            float slope, bool scatter, float* alpha, const float* et, hipStream_t st);
+hipError_t gatv2_attention(const ppgat_schedule& sch, const int32_t* col, const int32_t* eid, int H, int C,
+                           const float* xl, const float* xr, const float* att, const float* m, const float* invl,
+                           float slope, bool scatter, float* alpha, hipStream_t st);
+hipError_t attention_topk(const int32_t* rowptr, const int32_t* eid, const float* val, int64_t rows, int heads,
+                          int k, int32_t* out_eid, float* out_val, int32_t* out_cnt, hipStream_t st);
+
 hipError_t eval_sample(const int64_t* ptr, const int32_t* items_sorted, const int64_t* users, const int64_t* pos,
                        int64_t n_eval, int64_t n_neg, int64_t n_items, uint64_t seed, int64_t* cands, int32_t* bad,
                        hipStream_t st);

@@ -397,6 +397,68 @@ __global__ void __launch_bounds__(256) k_fwd_merge(const int32_t* __restrict__ h
 }
 
 // ---------------------------------------------------------------------------
+// Attention weights (ppgat_attention): alpha_k = exp(e_k - m_i) inv_l_i per edge and head, BEFORE
+// the dropout mask, from the forward's own final state -- the logit formed as k_fwd forms it
+// (logit() of (s_src[j] + s_dst[i]) [+ et[k]], that association order), so e_k <= m_i and the
+// largest weight of a PyG-mode destination is inv_l_i bit for bit.  No reduction: a hub piece is
+// just another item, nothing is merged.  One wave per item; its lanes stride over the item's
+// (edge, head) pairs, so the [E, H] output is written in whole lines at order 0 (scatter: at
+// eid[k], the caller's edge order -- 4 H bytes per edge wherever it falls).
+// ---------------------------------------------------------------------------
+template <bool EDGE>
+__global__ void __launch_bounds__(256) k_attn(Items it, const int32_t* __restrict__ col,
+                                              const int32_t* __restrict__ eid, int heads,
+                                              const float* __restrict__ s_src, const float* __restrict__ s_dst,
+                                              const float* __restrict__ m_in, const float* __restrict__ invl_in,
+                                              int mode, float slope, bool scatter, float* __restrict__ alpha,
+                                              const float* __restrict__ et) {
+  const int lane = threadIdx.x & 63;
+  const int64_t w = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (w >= it.n_items) return;
+  const int64_t i = it.row[w];
+  const int rs = it.beg[w];
+  const int total = (it.end[w] - rs) * heads;
+  const bool pyg = mode == kModePyg;
+  for (int t = lane; t < total; t += 64) {
+    const int q = t / heads, hd = t - q * heads;
+    const int k = rs + q;
+    float z = s_src[(int64_t)col[k] * heads + hd] + s_dst[i * heads + hd];
+    if constexpr (EDGE) z += et[(int64_t)k * heads + hd];
+    const float e = logit(z, slope, mode);
+    const float pe = pyg ? expf(e - m_in[i * heads + hd]) : expf(e);
+    const int64_t o = scatter ? eid[k] : k;
+    alpha[o * heads + hd] = pe * invl_in[i * heads + hd];
+  }
+}
+
+// The short items (<= 16 edges), four per wave: lane ql of a 16-lane row takes the edge rs + ql
+// and every head of it.  No cross-lane step, so a lane without an edge leaves at once.
+template <bool EDGE>
+__global__ void __launch_bounds__(256) k_attn_short(Items it, int64_t first, const int32_t* __restrict__ col,
+                                                    const int32_t* __restrict__ eid, int heads,
+                                                    const float* __restrict__ s_src,
+                                                    const float* __restrict__ s_dst, const float* __restrict__ m_in,
+                                                    const float* __restrict__ invl_in, int mode, float slope,
+                                                    bool scatter, float* __restrict__ alpha,
+                                                    const float* __restrict__ et) {
+  const int64_t item = first + (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
+  if (item >= it.n_items) return;
+  const int64_t i = it.row[item];
+  const int k = it.beg[item] + (threadIdx.x & 15);
+  if (k >= it.end[item]) return;
+  const bool pyg = mode == kModePyg;
+  const int64_t j = col[k];
+  const int64_t o = scatter ? eid[k] : k;
+  for (int hd = 0; hd < heads; ++hd) {
+    float z = s_src[j * heads + hd] + s_dst[i * heads + hd];
+    if constexpr (EDGE) z += et[(int64_t)k * heads + hd];
+    const float e = logit(z, slope, mode);
+    const float pe = pyg ? expf(e - m_in[i * heads + hd]) : expf(e);
+    alpha[o * heads + hd] = pe * invl_in[i * heads + hd];
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Backward prologue, one subgroup per (n, h), grid-stride over a fixed grid:
 //   D[n,h] = <g_n, agg[n,h]>, g = gscale * grad_out   (= sum_k alpha_k dalpha_k, Appendix B)
 // and the per-node state pass B gathers once per edge, packed as one float4:
@@ -1174,6 +1236,36 @@ hipError_t launch_fwd(const ppgat_schedule& sch, const int32_t* col, const int32
     PPGAT_DISPATCH_C(C, hipLaunchKernelGGL(k_fwd_merge<CC>, dim3(blocks_for(sch.n_hubs * 64)), dim3(256), 0, st,
                                            sch.hub_row, sch.hub_ptr, sch.n_hubs, heads, partial, bias, mode, eps, out,
                                            m, invl, agg));
+  }
+  return hipGetLastError();
+}
+
+// the long items (and hub pieces) one wave each, the short ones 16 lanes each when the schedule
+// counted them
+hipError_t launch_attention(const ppgat_schedule& sch, const int32_t* col, const int32_t* eid, int heads,
+                            const float* ss, const float* sd, const float* m, const float* invl, int mode,
+                            float slope, bool scatter, float* alpha, const float* et, hipStream_t st) {
+  if (sch.n_items <= 0) return hipSuccess;
+  const int64_t n_long =
+      sch.n_long_items >= sch.n_hub_items && sch.n_long_items <= sch.n_items ? sch.n_long_items : sch.n_items;
+  if (n_long > 0) {
+    const Items its = items_of(sch, n_long);
+    if (et != nullptr)
+      hipLaunchKernelGGL(k_attn<true>, dim3(blocks_for(n_long * 64)), dim3(256), 0, st, its, col, eid, heads, ss, sd,
+                         m, invl, mode, slope, scatter, alpha, et);
+    else
+      hipLaunchKernelGGL(k_attn<false>, dim3(blocks_for(n_long * 64)), dim3(256), 0, st, its, col, eid, heads, ss, sd,
+                         m, invl, mode, slope, scatter, alpha, et);
+  }
+  if (n_long < sch.n_items) {
+    const Items all = items_of(sch, sch.n_items);
+    const dim3 g(blocks_for((sch.n_items - n_long) * 16));
+    if (et != nullptr)
+      hipLaunchKernelGGL(k_attn_short<true>, g, dim3(256), 0, st, all, n_long, col, eid, heads, ss, sd, m, invl, mode,
+                         slope, scatter, alpha, et);
+    else
+      hipLaunchKernelGGL(k_attn_short<false>, g, dim3(256), 0, st, all, n_long, col, eid, heads, ss, sd, m, invl, mode,
+                         slope, scatter, alpha, et);
   }
   return hipGetLastError();
 }

@@ -334,6 +334,28 @@ def export_item_embeddings(model, item_feats: torch.Tensor, edge_index: torch.Te
         return Z[model.n_users:].detach().cpu().numpy().astype(np.float32)
 
 
+def attention_topk(model, item_feats: torch.Tensor, edge_index: torch.Tensor, k: int, layer: int = -1,
+                   edge_attr=None):
+    """The k (1..32) most-attended in-neighbours of every node in layer ``layer`` of a GAT model
+    (PyGGAT, PyGGATv2, CustomGAT): ``(src [N, k] int64, weight [N, k] fp32, count [N] int32)``.
+    src[i] are source node ids (edge_index[0] of the chosen edges), most attended first, ranked
+    by the head-mean attention weight (ties: the earlier edge_index column first), -1 past the
+    node's in-degree; weight the head means (0 in the pads); count = min(k, in-degree).  The
+    weights are the eval-mode ones (model.attention); they are computed in CSR slot order and
+    selected there (ppgat_attention_topk), so no [E, H] array in edge order is formed."""
+    from . import hip_ops
+    from .model import layer_attention
+    layers = model.convs if hasattr(model, "convs") else model.layers
+    if edge_attr is not None and getattr(model, "edge_dim", None) is None:
+        raise NotImplementedError(f"{type(model).__name__}: edge features are not implemented")
+    alpha, = layer_attention(model, layers, item_feats, edge_index, edge_attr, order="slot", only=int(layer))
+    graph = hip_ops.graph_cache.get(edge_index, model.n_users + item_feats.size(0))
+    eid, val, cnt = hip_ops.attention_topk(graph, alpha, int(k))
+    e = eid.long()
+    src = torch.where(e >= 0, edge_index[0][e.clamp_min(0)], e) if graph.n_edges else e
+    return src, val, cnt
+
+
 def top_k_batch(item_vecs: torch.Tensor, histories: Sequence[Sequence[int]], k: int = 20):
     """serving/runtime.py:56-76 for a batch of users on the device (ppgat_serve_topk): per
     history, the mean of its rows, scores over every item, the history masked to -1e9, the

@@ -517,6 +517,89 @@ def gatv2_aggregate(xl, xr, att, bias, graph, heads, channels, slope, dropout_p=
     return GATv2Aggregate.apply(xl, xr, att, bias, graph, heads, channels, float(slope), float(dropout_p), int(seed))
 
 
+# ---------------------------------------------------------------------------
+# attention weights (ppgat_attention, ppgat_dynatt_attention, ppgat_attention_topk)
+# ---------------------------------------------------------------------------
+_ORDERS = {"slot": 0, "edge": 1}
+
+
+def _attention_out(graph: CSRGraph, heads: int, order: str, dev):
+    _require(order in _ORDERS, f"order: expected 'edge' (edge_index column order) or 'slot' (CSR slot order), "
+                               f"got {order!r}")
+    return _ORDERS[order], torch.empty(graph.n_edges, heads, dtype=torch.float32, device=dev)
+
+
+def _check_state(graph: CSRGraph, heads: int, dev, **named):
+    for name, t in named.items():
+        _check_dev(name, t, torch.float32, dev)
+        _require(t.numel() == graph.n_nodes * heads, f"{name} must be [{graph.n_nodes}, {heads}]")
+
+
+def attention_weights(graph: CSRGraph, s_src, s_dst, m, inv_l, heads: int, mode: int, slope: float, edge_term=None,
+                      order: str = "edge") -> torch.Tensor:
+    """alpha [E, H] of a v1 layer (GATConv, SimpleGATLayer, the aggregate-then-transform layer):
+    the softmax weight of every edge and head BEFORE the dropout mask, recomputed from the node
+    scores and the softmax state (m, inv_l) a forward over those scores left (gat_fwd,
+    xgat_forward).  ``edge_term`` [E, H] in CSR slot order (edge_terms): the edge-feature logit
+    term.  ``order``: "edge" -- row k belongs to column k of the edge_index the graph was built
+    from -- or "slot" (CSR slot order, what attention_topk reads).  No gradient."""
+    heads = int(heads)
+    _check_dev("s_src", s_src, torch.float32)
+    dev = s_src.device
+    _require(1 <= heads <= 8, "heads must be in [1, 8]")
+    _require(s_src.numel() == graph.n_nodes * heads, f"s_src must be [{graph.n_nodes}, {heads}]")
+    _check_state(graph, heads, dev, s_dst=s_dst, m=m, inv_l=inv_l)
+    if edge_term is not None:
+        _check_dev("edge_term", edge_term, torch.float32, dev)
+        _require(edge_term.numel() >= graph.n_edges * heads, f"edge_term must be [{graph.n_edges}, {heads}]")
+    code, alpha = _attention_out(graph, heads, order, dev)
+    with torch.cuda.device(dev):
+        _launch.attention(graph, s_src, s_dst, m, inv_l, heads, int(mode), slope, code, alpha, edge_term)
+    return alpha
+
+
+def gatv2_attention_weights(graph: CSRGraph, xl, xr, att, m, inv_l, heads: int, channels: int, slope: float,
+                            order: str = "edge") -> torch.Tensor:
+    """alpha [E, H] of a GATv2 layer before the dropout mask, from the projections x_l, x_r
+    [N, H * C] and the state (m, inv_l) _launch.dynatt_fwd left for them; ``order`` as in
+    attention_weights.  No gradient."""
+    heads, channels = int(heads), int(channels)
+    _gatv2_require_shape(heads, channels)
+    _check_dev("xl", xl, torch.float32)
+    dev = xl.device
+    _check_dev("xr", xr, torch.float32, dev)
+    _check_dev("att", att, torch.float32, dev)
+    _require(tuple(xl.shape) == (graph.n_nodes, heads * channels),
+             f"xl must be [{graph.n_nodes}, {heads * channels}], got {tuple(xl.shape)}")
+    _require(tuple(xr.shape) == tuple(xl.shape), "xr must have xl's shape")
+    _require(att.numel() == heads * channels, "att must be [H, C]")
+    _check_state(graph, heads, dev, m=m, inv_l=inv_l)
+    code, alpha = _attention_out(graph, heads, order, dev)
+    with torch.cuda.device(dev):
+        _launch.dynatt_attention(graph, xl, xr, att, m, inv_l, heads, channels, slope, code, alpha)
+    return alpha
+
+
+def attention_topk(graph: CSRGraph, val_slot_order: torch.Tensor, k: int):
+    """(eid [N, k] int32, val [N, k], cnt [N] int32): per destination the k (1..32) in-edges with the
+    largest head mean of ``val_slot_order`` [E, H] (CSR slot order: attention_weights(...,
+    order="slot")), ranked exactly under (value descending, original edge id ascending); eid are
+    edge_index column ids, -1 (value 0) past the in-degree; cnt = min(k, in-degree)."""
+    _check_dev("val_slot_order", val_slot_order, torch.float32)
+    dev = val_slot_order.device
+    E, N = graph.n_edges, graph.n_nodes
+    _require(val_slot_order.dim() == 2 and val_slot_order.size(0) == E and 1 <= val_slot_order.size(1) <= 8,
+             f"val_slot_order must be [{E}, H <= 8], got {tuple(val_slot_order.shape)}")
+    _require(isinstance(k, int) and 1 <= k <= 32, "k must be an int in [1, 32]")
+    _require(graph.rowptr.device == dev, f"val_slot_order: on {dev}, the graph on {graph.rowptr.device}")
+    eid = torch.empty(N, k, dtype=torch.int32, device=dev)
+    val = torch.empty(N, k, dtype=torch.float32, device=dev)
+    cnt = torch.empty(N, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _launch.attention_topk(graph, val_slot_order, val_slot_order.size(1), k, eid, val, cnt)
+    return eid, val, cnt
+
+
 def _bwd_edges_src(g: CSRGraph, sched: Schedule, r0: int, h, s_src, nstate, grad_out, D, S, dz, heads, channels,
                    mode, slope, p, seed, seed_buf=None, edge_term=None):
     """Pass B over the source rows of ``sched`` (row ids relative to r0; edge slots and
@@ -942,6 +1025,72 @@ def gat_layer(x, weight, att_src, att_dst, bias, graph, heads, channels, mode, s
                            dropout_p, seed)
     return GATLayer.apply(x, weight, att_src, att_dst, bias, graph, heads, channels, mode, slope, dropout_p, seed,
                           x_items, rep)
+
+
+def gat_layer_attention(x, weight, att_src, att_dst, graph, heads, channels, mode, slope, x_items=None, edge_v=None,
+                        edge_attr=None, order: str = "edge") -> torch.Tensor:
+    """alpha [E, H] of gat_layer(x, ...) on the same arguments, before the dropout mask: a
+    no-grad forward of its own over the unfused primitives (projection and node scores, the
+    edge terms, gat_fwd -- xgat_forward where gat_layer takes the aggregate-then-transform
+    path) whose scores and softmax state go to attention_weights.  Costs a second forward."""
+    _require(x.is_cuda, "gat_layer_attention: ppgat runs on ROCm devices only; there is no CPU path")
+    if x.dtype != torch.float32 or x.dim() != 2:
+        raise NotImplementedError("ppgat gat_layer_attention: fp32 2-D input only")
+    if (edge_v is None) != (edge_attr is None):
+        raise ValueError("gat_layer_attention: edge_v and edge_attr go together")
+    if edge_v is not None and mode != _lib.MODE_PYG:
+        raise NotImplementedError("gat_layer_attention: edge features are GATConv's (PyG mode) only")
+    heads, channels = int(heads), int(channels)
+    with torch.no_grad(), torch.cuda.device(x.device):
+        x = x.detach().contiguous()
+        x_items = x_items.detach().contiguous() if x_items is not None else None
+        W = weight.detach().contiguous()
+        a_s = att_src.detach().reshape(heads, channels).contiguous()
+        a_d = att_dst.detach().reshape(heads, channels).contiguous()
+        K = x.size(1)
+        if (edge_v is None and mode == _lib.MODE_PYG and heads > 1 and heads * channels > K
+                and xgat_supported(K, heads, channels)):
+            global KINK_TAP
+            xx = join_rows(x, x_items) if x_items is not None else x
+            tap, KINK_TAP = KINK_TAP, None  # the instrumentation records the layer's own forward only
+            try:
+                _, st = xgat_forward(xx, W, a_s, a_d, None, XViews.of_graph(graph), heads, channels, slope, 0.0, 0,
+                                     keep_agg=False)
+            finally:
+                KINK_TAP = tap
+            return attention_weights(graph, st["s_src"], st["s_dst"], st["m"], st["inv_l"], heads, mode, slope,
+                                     order=order)
+        if heads == 1 and project_supported(K, channels) and (x_items is None or x_items.size(1) == K):
+            h, s_src, s_dst = project(x, W, att_src=a_s, att_dst=a_d, x_items=x_items)
+            s_src, s_dst = s_src.view(-1, 1), s_dst.view(-1, 1)
+        else:
+            if x_items is not None:
+                x = torch.cat([x, x_items], 0)
+            h = mm_nn(x, W, 1, heads * channels)
+            s_src, s_dst = node_scores(h, a_s, a_d, heads, channels)
+        t_csr = None
+        if edge_v is not None:
+            staged = stage_edge_attr(graph, edge_attr)
+            t_csr, _ = edge_terms(graph, staged, edge_v.detach().reshape(heads, -1).contiguous(), heads, want_csc=False)
+        _, m, inv_l, _ = gat_fwd(graph, h, s_src, s_dst, None, heads, channels, mode, slope, 0.0, 0, want_agg=False,
+                                 edge_term=t_csr)
+        return attention_weights(graph, s_src, s_dst, m, inv_l, heads, mode, slope, edge_term=t_csr, order=order)
+
+
+def gatv2_layer_attention(xl, xr, att, graph, heads, channels, slope, order: str = "edge") -> torch.Tensor:
+    """alpha [E, H] of gatv2_aggregate(xl, xr, att, ...) before the dropout mask: a no-grad
+    aggregate of its own (_launch.dynatt_fwd) whose state goes to gatv2_attention_weights."""
+    heads, channels = int(heads), int(channels)
+    _gatv2_require_shape(heads, channels)
+    _require(xl.is_cuda, "gatv2_layer_attention: ppgat runs on ROCm devices only; there is no CPU path")
+    with torch.no_grad(), torch.cuda.device(xl.device):
+        shared = xr is xl or (xr.data_ptr() == xl.data_ptr() and xr.stride() == xl.stride())
+        xl = xl.detach().contiguous()
+        xr = xl if shared else xr.detach().contiguous()
+        att_c = att.detach().contiguous().view(heads, channels)
+        out, m, inv_l, _ = _fwd_outputs(graph.n_nodes, heads, channels, False, xl.device)
+        _launch.dynatt_fwd(graph, xl, xr, att_c, None, heads, channels, slope, 0.0, 0, None, out, m, inv_l)
+        return gatv2_attention_weights(graph, xl, xr, att_c, m, inv_l, heads, channels, slope, order=order)
 
 
 # ---------------------------------------------------------------------------

@@ -91,6 +91,36 @@ def _stack(model, item_proj, item_feats, layers, edge_index, edge_attr=None):
     return x
 
 
+def layer_attention(model, layers, item_feats, edge_index, edge_attr=None, order: str = "edge", only=None):
+    """The attention weights of a model's layer stack: a list with one [E, H] fp32 tensor per layer
+    (``only``: that layer alone, the stack run no further), alpha before the dropout mask, row k
+    for column k of ``edge_index`` (``order="slot"``: CSR slot order).  Runs in eval mode under
+    no_grad -- the weights a served model would use -- and puts every module's training flag
+    back afterwards.  Per layer the weights cost a second forward (``layer.attention``)."""
+    ea = {} if edge_attr is None else {"edge_attr": edge_attr}
+    n = len(layers)
+    if only is not None:
+        if not -n <= only < n:
+            raise IndexError(f"layer {only} of a {n}-layer model")
+        only = only % n
+    flags = [(mod, mod.training) for mod in model.modules()]
+    model.eval()
+    try:
+        with torch.no_grad():
+            x = model.node_features(item_feats)
+            out = []
+            for l, layer in enumerate(layers):
+                if only is None or l == only:
+                    out.append(layer.attention(x, edge_index, order=order, **ea))
+                if l == n - 1 or l == only:
+                    break
+                x = layer(x, edge_index, **ea)
+    finally:
+        for mod, was in flags:
+            mod.training = was
+    return out
+
+
 class PyGGAT(torch.nn.Module):
     def __init__(self, n_users: int, n_items: int, item_feat_dim: int, hidden: int, layers: int, heads: int,
                  attn_dropout: float, edge_dim=None):
@@ -113,6 +143,10 @@ class PyGGAT(torch.nn.Module):
 
     def forward(self, item_feats: torch.Tensor, edge_index: torch.Tensor, edge_attr=None) -> torch.Tensor:
         return _stack(self, self.item_proj, item_feats, self.convs, edge_index, edge_attr)
+
+    def attention(self, item_feats: torch.Tensor, edge_index: torch.Tensor, edge_attr=None, order: str = "edge"):
+        """One [E, H] attention tensor per layer (layer_attention)."""
+        return layer_attention(self, self.convs, item_feats, edge_index, edge_attr, order)
 
 
 class PyGGATv2(torch.nn.Module):
@@ -140,6 +174,12 @@ class PyGGATv2(torch.nn.Module):
     def forward(self, item_feats: torch.Tensor, edge_index: torch.Tensor) -> torch.Tensor:
         return _stack(self, self.item_proj, item_feats, self.convs, edge_index)
 
+    def attention(self, item_feats: torch.Tensor, edge_index: torch.Tensor, edge_attr=None, order: str = "edge"):
+        """One [E, H] attention tensor per layer (layer_attention); GATv2Conv takes no ``edge_attr``."""
+        if edge_attr is not None:
+            raise NotImplementedError("PyGGATv2: edge features are not implemented")
+        return layer_attention(self, self.convs, item_feats, edge_index, None, order)
+
 
 class CustomGAT(torch.nn.Module):
     def __init__(self, n_users: int, n_items: int, item_feat_dim: int, hidden: int, layers: int):
@@ -158,6 +198,12 @@ class CustomGAT(torch.nn.Module):
 
     def forward(self, item_feats: torch.Tensor, edge_index: torch.Tensor) -> torch.Tensor:
         return _stack(self, self.item_proj, item_feats, self.layers, edge_index)
+
+    def attention(self, item_feats: torch.Tensor, edge_index: torch.Tensor, edge_attr=None, order: str = "edge"):
+        """One [E, 1] attention tensor per layer (layer_attention); the custom layer takes no ``edge_attr``."""
+        if edge_attr is not None:
+            raise NotImplementedError("CustomGAT: edge features are not implemented")
+        return layer_attention(self, self.layers, item_feats, edge_index, None, order)
 
 
 def bpr_loss(Z: torch.Tensor, n_users: int, u, i, j, loss: str = "bpr", prepared=None) -> torch.Tensor:

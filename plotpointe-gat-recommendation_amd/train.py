@@ -362,6 +362,23 @@ def write_recommendations(args, cfg: Config, model, item_feats, edge_index, tr, 
     return {"path": str(path), "k": k, f"coverage@{k}": float(len(np.unique(idx[idx >= 0]))) / float(n_items)}
 
 
+def write_attention(args, cfg: Config, model, item_feats, edge_index, n_users: int, n_items: int, edge_attr=None):
+    """--attention-out: for every user, the --attention-k most-attended in-neighbours of the last
+    layer (evaluation.attention_topk; in a user-item graph a user's in-neighbours are the items
+    it interacted with), written as an .npz with ``users`` [n_users], ``items`` [n_users, K] (item
+    ids, -1 = fewer than K in-edges; a neighbour that is not an item node is -1 too), ``weights``
+    (head-mean attention, 0 in the pads) and ``count``.  Returns the run record's "attention" entry."""
+    k = int(args.attention_k)
+    src, w, cnt = evaluation.attention_topk(model, item_feats, edge_index, k, layer=-1, edge_attr=edge_attr)
+    src, w, cnt = src[:n_users].cpu().numpy(), w[:n_users].cpu().numpy(), cnt[:n_users].cpu().numpy()
+    items = np.where((src >= n_users) & (src < n_users + n_items), src - n_users, -1).astype(np.int64)
+    path = Path(args.attention_out)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "wb") as f:
+        np.savez(f, users=np.arange(n_users, dtype=np.int64), items=items, weights=w, count=cnt)
+    return {"path": str(path), "k": k, "layer": cfg.layers - 1, "mean_count": float(cnt.mean()) if len(cnt) else 0.0}
+
+
 def main_lightgcn(args):
     """train_lightgcn.py main(): the mini-batch loop over every positive x neg_per_pos
     (:313-336), sampled evaluation each epoch, best-val checkpoint on ndcg@20, reload, test."""
@@ -548,6 +565,10 @@ def build_parser():
                     help="after the test evaluation, write every user's --recommend-k best items outside the train "
                          "history (ppgat_full_topk) to this .npz; one GPU")
     ap.add_argument("--recommend-k", type=int, default=20)
+    ap.add_argument("--attention-out", default=None, metavar="PATH",
+                    help="after training, write every user's --attention-k most-attended items of the last layer "
+                         "(ppgat_attention_topk) to this .npz; one GPU, GAT families only")
+    ap.add_argument("--attention-k", type=int, default=10)
     return ap
 
 
@@ -559,6 +580,14 @@ def main(argv=None):
     if args.recommend_out and args.world_size > 1:
         raise NotImplementedError("--recommend-out runs on one GPU (--world-size 1): the lists are made from the "
                                   "whole user and item tables")
+    if args.attention_out and args.world_size > 1:
+        raise NotImplementedError("--attention-out runs on one GPU (--world-size 1): the sharded models return no "
+                                  "attention weights")
+    if args.attention_out and args.model_family == "lightgcn":
+        raise NotImplementedError("--attention-out with --model-family lightgcn is not implemented: LightGCN has no "
+                                  "attention weights")
+    if args.attention_out and not 1 <= args.attention_k <= 32:
+        raise ValueError(f"--attention-k {args.attention_k}: expected 1..32")
     full = args.eval_mode == "full"
     if full and args.world_size > 1:
         raise NotImplementedError("--eval-mode full runs on one GPU (the sharded trainers evaluate sampled)")
@@ -730,6 +759,9 @@ def main(argv=None):
     if args.recommend_out:  # one GPU (refused above otherwise)
         out["recommendations"] = write_recommendations(args, cfg, model, item_feats, edge_index, tr, n_users, n_items,
                                                        dev_sampler, device, edge_attr=edge_attr)
+    if args.attention_out:  # one GPU (refused above otherwise)
+        out["attention"] = write_attention(args, cfg, model, item_feats, edge_index, n_users, n_items,
+                                           edge_attr=edge_attr)
     if world > 1:
         import torch.distributed as tdist
         tdist.destroy_process_group()
