@@ -711,6 +711,60 @@ int ppgat_weighted_eval_sample(const int64_t* user_ptr, const int32_t* items_sor
                                const int64_t* pos, int64_t n_eval, int64_t n_neg, int64_t n_items,
                                const uint64_t* cdf, uint64_t seed, int64_t* cands, int32_t* bad, void* stream);
 
+/* ---- fan-out neighbour sampling: a per-epoch sampled graph, derived without a sort --------
+ * Replaces: nothing in the reference, which trains on the whole graph at every step; the path it
+ *   spares is ppgat_csr_build (two radix sorts) over a resampled edge_index each epoch.
+ * The rule.  Destination i with in-degree d = rowptr[i + 1] - rowptr[i] and cap f (f = fanout,
+ *   or fanout_of[i] where fanout_of is given and its entry is >= 0; an entry < 0 keeps all; 0
+ *   keeps nothing) numbers its in-edges p = 0 .. d - 1 in CSR slot order (ascending original edge
+ *   id: the build's sort is stable).  d <= f keeps every in-edge.  d > f keeps the positions of
+ *   Robert Floyd's subset S over the counter stream of ppgat_bpr_sample:
+ *     S = {};  for s = 0 .. f - 1:  j = d - f + s;  t = mulhi64(draw64(seed, i, s), j + 1);
+ *                                   add (t in S ? j : t) to S
+ *   so every f-subset is equally likely, a row's sample depends on (seed, i, d, f) alone -- never
+ *   on the launch geometry -- and a row costs f draws, not d.  One wave per such row: lane s
+ *   holds element s of S and membership is a compare plus a 64-bit ballot, hence
+ *   f <= ppgat_neighbor_max_fanout() = 64.  Rows with d <= f are copied by a streaming pass over
+ *   the sampled slots and pay no wave.
+ * The sampled graph: its edges are the kept ones in ascending original edge id, renumbered
+ *   0 .. E' - 1 (new id = exclusive scan of the keep flags in edge-id order).  Every array written
+ *   equals, element for element, what ppgat_csr_build gives for edge_index_s, and
+ *   csr2csc_s what ppgat_invert_index gives for csc2csr_s.
+ * Three calls on one stream share one workspace (ppgat_neighbor_sample_workspace_bytes(n_nodes,
+ * n_edges), host-only), which the caller leaves untouched between them:
+ * ppgat_neighbor_count: rowptr_s [n_nodes + 1] = exclusive scan of min(d, f); info [2] int32 =
+ *   {E' = rowptr_s[n_nodes], bad}; bad = 1 if some fanout_of entry exceeds the maximum (that row
+ *   is then counted as if capped at the maximum and the caller must not go on).  The caller's
+ *   read of info is the only host sync these entries need: E' sizes the outputs of the other two.
+ * ppgat_neighbor_sample: rowptr, col, csr_eid [n_edges] the parent's CSR, csr2csc [n_edges] the CSC
+ *   slot of each CSR slot (ppgat_invert_index of csc2csr), edge_index [2, n_edges] int64 what the
+ *   parent was built from, rowptr_s and n_kept = E' from the count.  Writes col_s,
+ *   csr_eid_s [E'] (new numbering), edge_index_s [2, E'] int64 (the kept columns) and eid [E']
+ *   int64 (their original ids, so edge_attr[eid] is the sampled graph's attribute tensor).
+ * ppgat_neighbor_derive: colptr, row, csc_eid, csc2csr the parent's CSC.  Writes colptr_s
+ *   [n_nodes + 1], row_s, csc_eid_s, csc2csr_s, csr2csc_s [E'] (a scan of the keep flags the
+ *   pick left in CSC order, plus a scatter).  The schedules are ppgat_schedule_build over rowptr_s / colptr_s.
+ * Refused before any device work: fanout outside [1, max] -> PPGAT_ERR_UNSUPPORTED; a negative
+ *   size, n_kept > n_edges, a NULL required pointer (the per-edge ones only when n_edges, resp.
+ *   n_kept, > 0; fanout_of may be NULL) or a short workspace -> PPGAT_ERR_INVALID; sizes >= 2^31
+ *   -> PPGAT_ERR_UNSUPPORTED.  No float anywhere, no atomics on data: two calls give the same
+ *   bits.  Nothing past an output's stated length is written.  The debug build validates
+ *   rowptr / colptr / rowptr_s and the parent's index arrays first. */
+int ppgat_neighbor_max_fanout(void);
+int ppgat_neighbor_sample_workspace_bytes(int64_t n_nodes, int64_t n_edges, size_t* bytes);
+int ppgat_neighbor_count(const int32_t* rowptr, int64_t n_nodes, int64_t n_edges, int fanout,
+                         const int32_t* fanout_of, int32_t* rowptr_s, int32_t* info, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int ppgat_neighbor_sample(const int32_t* rowptr, const int32_t* col, const int32_t* csr_eid,
+                          const int32_t* csr2csc, const int64_t* edge_index, int64_t n_nodes, int64_t n_edges, uint64_t seed,
+                          const int32_t* rowptr_s, int64_t n_kept, int32_t* col_s, int32_t* csr_eid_s,
+                          int64_t* edge_index_s, int64_t* eid, void* workspace, size_t workspace_bytes,
+                          void* stream);
+int ppgat_neighbor_derive(const int32_t* colptr, const int32_t* row, const int32_t* csc_eid, const int32_t* csc2csr,
+                          int64_t n_nodes, int64_t n_edges, int64_t n_kept, int32_t* colptr_s, int32_t* row_s,
+                          int32_t* csc_eid_s, int32_t* csc2csr_s, int32_t* csr2csc_s, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
 /* ---- sampled ranking (evaluation) ------------------------------------------------
  * Replaces: the per-user loop of eval_sampled, scripts/train_gat_pyg.py:160-175:
  *   scores = I[cands[b]] @ U[users[b]];  rank[b] = #(scores[1:] > scores[0]) + 1

@@ -8,15 +8,16 @@ import it is also registered as ``ppgat_amd``.
 """
 import sys as _sys
 
-from . import _lib, data, dist, evaluation, fusion, knn, lightgcn, optim, sampler, torch_ops  # noqa: F401
+from . import _lib, data, dist, evaluation, fusion, knn, lightgcn, neighbors, optim, sampler, torch_ops  # noqa: F401
 from .conv import GATConv, GATv2Conv, SimpleGATLayer  # noqa: F401
 from .evaluation import eval_full, eval_topk, full_rank, recommend_topk, topk_metrics  # noqa: F401
 from .hip_ops import CSRGraph, csr_build, gat_aggregate, gatv2_aggregate, graph_cache  # noqa: F401
 from .lightgcn import LightGCN  # noqa: F401
+from .neighbors import NeighborSampler, sample_neighbors  # noqa: F401
 from .model import CustomGAT, PyGGAT, PyGGATv2, bpr_loss, shared_softmax_loss, softmax_loss  # noqa: F401
 
 _sys.modules.setdefault("ppgat_amd", _sys.modules[__name__])
 
 __all__ = ["GATConv", "GATv2Conv", "SimpleGATLayer", "PyGGAT", "PyGGATv2", "CustomGAT", "LightGCN", "lightgcn", "bpr_loss", "softmax_loss", "shared_softmax_loss", "CSRGraph", "csr_build",
            "gat_aggregate", "gatv2_aggregate", "graph_cache", "data", "eval_full", "full_rank", "recommend_topk",
-           "topk_metrics", "eval_topk"]
+           "topk_metrics", "eval_topk", "NeighborSampler", "sample_neighbors"]

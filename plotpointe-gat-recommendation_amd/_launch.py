@@ -191,6 +191,38 @@ def attention_topk(g, val, heads: int, k: int, out_eid, out_val, out_cnt):
           "attention_topk")
 
 
+# fan-out neighbour sampling (ppgat_neighbor_*); ``g``: the parent hip_ops.CSRGraph.  The three
+# run in this order on one stream and share ``ws`` (neighbor_workspace), untouched in between.
+def neighbor_workspace(n_nodes: int, n_edges: int, dev):
+    return workspace(load().ppgat_neighbor_sample_workspace_bytes, n_nodes, n_edges, device=dev, floor=1)
+
+
+def neighbor_count(g, fanout: int, fanout_of, rowptr_s, info, ws, nbytes: int):
+    """rowptr_s [N + 1] and info [2] int32 = (E', bad) for the caps ``fanout`` / ``fanout_of``."""
+    check(load().ppgat_neighbor_count(ptr(g.rowptr), g.n_nodes, g.n_edges, int(fanout), ptr(fanout_of),
+                                      ptr(rowptr_s), ptr(info), ptr(ws), nbytes, stream_handle(rowptr_s.device)),
+          "neighbor_count")
+
+
+def neighbor_sample(g, edge_index, seed, rowptr_s, n_kept: int, col_s, csr_eid_s, edge_index_s, eid, ws, nbytes: int):
+    """The pick and the renumbering: the sampled CSR side, edge_index_s [2, E'] and eid [E'].
+    ``g.csr2csc`` must be there (hip_ops.csr_build leaves it; hip_ops._csr2csc makes it)."""
+    E = g.n_edges
+    check(load().ppgat_neighbor_sample(ptr(g.rowptr), *edge_ptrs(E, g.col, g.csr_eid, g.csr2csc, edge_index), g.n_nodes,
+                                       E,
+                                       seed64(seed), ptr(rowptr_s),
+                                       n_kept, *edge_ptrs(n_kept, col_s, csr_eid_s, edge_index_s, eid), ptr(ws), nbytes,
+                                       stream_handle(rowptr_s.device)), "neighbor_sample")
+
+
+def neighbor_derive(g, n_kept: int, colptr_s, row_s, csc_eid_s, csc2csr_s, csr2csc_s, ws, nbytes: int):
+    """The sampled CSC side and the slot maps between the two."""
+    E = g.n_edges
+    check(load().ppgat_neighbor_derive(ptr(g.colptr), *edge_ptrs(E, g.row, g.csc_eid, g.csc2csr), g.n_nodes, E, n_kept,
+                                       ptr(colptr_s), *edge_ptrs(n_kept, row_s, csc_eid_s, csc2csr_s, csr2csc_s),
+                                       ptr(ws), nbytes, stream_handle(colptr_s.device)), "neighbor_derive")
+
+
 # the aggregate-then-transform layer (ppgat_xgat_*); ``v``: a hip_ops.XViews
 def xgat_weights(W, a_s, a_d, H: int, C: int, A=None, Wt=None, Wg=None):
     """Whichever of A [2, H, K] (needs a_s, a_d), Wt [H * K, C] and Wg [C, H * K] are given."""

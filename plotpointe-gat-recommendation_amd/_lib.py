@@ -148,6 +148,13 @@ SIGNATURES = {
                                           c_vp, c_vp]),
     "ppgat_weighted_eval_sample": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_u64, c_vp, c_vp,
                                            c_vp]),
+    "ppgat_neighbor_max_fanout": (c_int, []),
+    "ppgat_neighbor_sample_workspace_bytes": (c_int, [c_i64, c_i64, ctypes.POINTER(c_sz)]),
+    "ppgat_neighbor_count": (c_int, [c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "ppgat_neighbor_sample": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_u64, c_vp, c_i64, c_vp, c_vp, c_vp,
+                                      c_vp, c_vp, c_sz, c_vp]),
+    "ppgat_neighbor_derive": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                      c_vp, c_sz, c_vp]),
     "ppgat_sampled_rank": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "ppgat_full_rank_supported": (c_int, [c_int]),
     "ppgat_full_rank_workspace_bytes": (c_int, [c_i64, c_i64, c_int, ctypes.POINTER(c_sz)]),

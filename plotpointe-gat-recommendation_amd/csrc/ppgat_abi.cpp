@@ -1410,6 +1410,87 @@ int ppgat_attention_topk(const int32_t* rowptr, const int32_t* csr_eid, const fl
   return PPGAT_OK;
 }
 
+int ppgat_neighbor_max_fanout(void) { return ppgat::kMaxFanout; }
+
+static int neighbor_sizes(int64_t n_nodes, int64_t n_edges, int64_t n_kept, const char* who) {
+  if (n_nodes < 0 || n_edges < 0 || n_kept < 0 || n_kept > n_edges)
+    return fail(PPGAT_ERR_INVALID, std::string(who) + ": bad sizes (0 <= n_kept <= n_edges, n_nodes >= 0)");
+  if (n_nodes >= (int64_t)1 << 31 || n_edges >= (int64_t)1 << 31)
+    return fail(PPGAT_ERR_UNSUPPORTED, std::string(who) + ": nodes and edges must be < 2^31");
+  return 0;
+}
+
+int ppgat_neighbor_sample_workspace_bytes(int64_t n_nodes, int64_t n_edges, size_t* bytes) {
+  if (!bytes) return fail(PPGAT_ERR_INVALID, "neighbor_sample_workspace_bytes: null pointer");
+  if (int rc = neighbor_sizes(n_nodes, n_edges, 0, "neighbor_sample_workspace_bytes")) return rc;
+  *bytes = ppgat::neighbor_workspace_bytes(n_nodes, n_edges);
+  return PPGAT_OK;
+}
+
+int ppgat_neighbor_count(const int32_t* rowptr, int64_t n_nodes, int64_t n_edges, int fanout,
+                         const int32_t* fanout_of, int32_t* rowptr_s, int32_t* info, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+  if (fanout < 1 || fanout > ppgat::kMaxFanout)
+    return fail(PPGAT_ERR_UNSUPPORTED, "neighbor_count: fanout must be in [1, 64] (one lane per kept neighbour)");
+  if (int rc = neighbor_sizes(n_nodes, n_edges, 0, "neighbor_count")) return rc;
+  if (!rowptr || !rowptr_s || !info) return fail(PPGAT_ERR_INVALID, "neighbor_count: null pointer");
+  if (!workspace || workspace_bytes < ppgat::neighbor_workspace_bytes(n_nodes, n_edges))
+    return fail(PPGAT_ERR_INVALID, "neighbor_count: workspace too small");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = debug_range(rowptr, 4, n_nodes + 1, 0, n_edges + 1, "neighbor_count: rowptr", st)) return rc;
+  Timed t(PPGAT_K_SAMPLE, st);
+  hipError_t e = ppgat::neighbor_count(rowptr, n_nodes, fanout, fanout_of, rowptr_s, info, workspace, workspace_bytes,
+                                       st);
+  if (e != hipSuccess) return hip_fail(e, "neighbor_count");
+  return PPGAT_OK;
+}
+
+int ppgat_neighbor_sample(const int32_t* rowptr, const int32_t* col, const int32_t* csr_eid,
+                          const int32_t* csr2csc, const int64_t* edge_index, int64_t n_nodes, int64_t n_edges, uint64_t seed,
+                          const int32_t* rowptr_s, int64_t n_kept, int32_t* col_s, int32_t* csr_eid_s,
+                          int64_t* edge_index_s, int64_t* eid, void* workspace, size_t workspace_bytes,
+                          void* stream) {
+  if (int rc = neighbor_sizes(n_nodes, n_edges, n_kept, "neighbor_sample")) return rc;
+  if (!rowptr || !rowptr_s || (n_edges > 0 && (!col || !csr_eid || !csr2csc || !edge_index)) ||
+      (n_kept > 0 && (!col_s || !csr_eid_s || !edge_index_s || !eid)))
+    return fail(PPGAT_ERR_INVALID, "neighbor_sample: null pointer");
+  if (!workspace || workspace_bytes < ppgat::neighbor_workspace_bytes(n_nodes, n_edges))
+    return fail(PPGAT_ERR_INVALID, "neighbor_sample: workspace too small");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = debug_range(rowptr, 4, n_nodes + 1, 0, n_edges + 1, "neighbor_sample: rowptr", st)) return rc;
+  if (int rc = debug_range(rowptr_s, 4, n_nodes + 1, 0, n_kept + 1, "neighbor_sample: rowptr_s", st)) return rc;
+  if (int rc = debug_range(col, 4, n_edges, 0, n_nodes, "neighbor_sample: col", st)) return rc;
+  if (int rc = debug_range(csr_eid, 4, n_edges, 0, n_edges, "neighbor_sample: csr_eid", st)) return rc;
+  if (int rc = debug_range(csr2csc, 4, n_edges, 0, n_edges, "neighbor_sample: csr2csc", st)) return rc;
+  Timed t(PPGAT_K_SAMPLE, st);
+  hipError_t e = ppgat::neighbor_sample(rowptr, col, csr_eid, csr2csc, edge_index, n_nodes, n_edges, seed, rowptr_s, n_kept,
+                                        col_s, csr_eid_s, edge_index_s, eid, workspace, workspace_bytes, st);
+  if (e != hipSuccess) return hip_fail(e, "neighbor_sample");
+  return PPGAT_OK;
+}
+
+int ppgat_neighbor_derive(const int32_t* colptr, const int32_t* row, const int32_t* csc_eid, const int32_t* csc2csr,
+                          int64_t n_nodes, int64_t n_edges, int64_t n_kept, int32_t* colptr_s, int32_t* row_s,
+                          int32_t* csc_eid_s, int32_t* csc2csr_s, int32_t* csr2csc_s, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+  if (int rc = neighbor_sizes(n_nodes, n_edges, n_kept, "neighbor_derive")) return rc;
+  if (!colptr || !colptr_s || (n_edges > 0 && (!row || !csc_eid || !csc2csr)) ||
+      (n_kept > 0 && (!row_s || !csc_eid_s || !csc2csr_s || !csr2csc_s)))
+    return fail(PPGAT_ERR_INVALID, "neighbor_derive: null pointer");
+  if (!workspace || workspace_bytes < ppgat::neighbor_workspace_bytes(n_nodes, n_edges))
+    return fail(PPGAT_ERR_INVALID, "neighbor_derive: workspace too small");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = debug_range(colptr, 4, n_nodes + 1, 0, n_edges + 1, "neighbor_derive: colptr", st)) return rc;
+  if (int rc = debug_range(row, 4, n_edges, 0, n_nodes, "neighbor_derive: row", st)) return rc;
+  if (int rc = debug_range(csc_eid, 4, n_edges, 0, n_edges, "neighbor_derive: csc_eid", st)) return rc;
+  if (int rc = debug_range(csc2csr, 4, n_edges, 0, n_edges, "neighbor_derive: csc2csr", st)) return rc;
+  Timed t(PPGAT_K_SAMPLE, st);
+  hipError_t e = ppgat::neighbor_derive(colptr, row, csc_eid, csc2csr, n_nodes, n_edges, n_kept, colptr_s, row_s,
+                                        csc_eid_s, csc2csr_s, csr2csc_s, workspace, workspace_bytes, st);
+  if (e != hipSuccess) return hip_fail(e, "neighbor_derive");
+  return PPGAT_OK;
+}
+
 int ppgat_eval_sample(const int64_t* user_ptr, const int32_t* items_sorted, const int64_t* users, const int64_t* pos,
                       int64_t n_eval, int64_t n_neg, int64_t n_items, uint64_t seed, int64_t* cands, int32_t* bad,
                       void* stream) {

@@ -220,6 +220,21 @@ hipError_t weighted_eval_sample(const int64_t* ptr, const int32_t* items_sorted,
                                 const int64_t* pos, int64_t n_eval, int64_t n_neg, int64_t n_items,
                                 const uint64_t* cdf, uint64_t seed, int64_t* cands, int32_t* bad, hipStream_t st);
 
+// fan-out neighbour sampling (ppgat_nsample.hip): a sampled graph's views compacted out of its
+// parent's, no sort.  count -> (host reads info[0] = E') -> sample -> derive, one workspace
+// (neighbor_workspace_bytes) carried through the three untouched in between.
+constexpr int kMaxFanout = 64;
+size_t neighbor_workspace_bytes(int64_t N, int64_t E);
+hipError_t neighbor_count(const int32_t* rowptr, int64_t N, int fanout, const int32_t* fanout_of, int32_t* rowptr_s,
+                          int32_t* info, void* ws, size_t ws_bytes, hipStream_t st);
+hipError_t neighbor_sample(const int32_t* rowptr, const int32_t* col, const int32_t* csr_eid,
+                           const int32_t* csr2csc, const int64_t* ei, int64_t N, int64_t E, uint64_t seed,
+                           const int32_t* rowptr_s, int64_t Es, int32_t* col_s, int32_t* csr_eid_s, int64_t* ei_s,
+                           int64_t* eid, void* ws, size_t ws_bytes, hipStream_t st);
+hipError_t neighbor_derive(const int32_t* colptr, const int32_t* row, const int32_t* csc_eid, const int32_t* csc2csr,
+                           int64_t N, int64_t E, int64_t Es, int32_t* colptr_s, int32_t* row_s, int32_t* csc_eid_s,
+                           int32_t* csc2csr_s, int32_t* csr2csc_s, void* ws, size_t ws_bytes, hipStream_t st);
+
 // evaluation (ppgat_eval.hip)
 hipError_t serve_topk(const float* iv, int64_t n_items, int C, const int64_t* hptr, const int64_t* hist,
                       int64_t max_hist, int B, int k, float* U, float* scores, int32_t* out_idx, float* out_score,

@@ -216,6 +216,24 @@ class _GraphCache:
             self.entries.pop(0)
         return g
 
+    @staticmethod
+    def _key(edge_index: torch.Tensor, n_nodes: int):
+        return (edge_index.data_ptr(), edge_index._version, tuple(edge_index.shape), int(n_nodes),
+                str(edge_index.device))
+
+    def put(self, edge_index: torch.Tensor, n_nodes: int, graph: CSRGraph):
+        """Register a graph made elsewhere (neighbors.NeighborSampler's derived one) under
+        ``edge_index``: ``get`` then returns it without a csr_build.  Replaces an entry of the
+        same tensor."""
+        self.drop(edge_index)
+        self.entries.append((self._key(edge_index, n_nodes), edge_index, graph))
+        if len(self.entries) > self.capacity:
+            self.entries.pop(0)
+
+    def drop(self, edge_index: torch.Tensor):
+        """Forget the entries of this very tensor (no-op when there is none)."""
+        self.entries = [t for t in self.entries if t[1] is not edge_index]
+
     def clear(self):
         self.entries.clear()
 

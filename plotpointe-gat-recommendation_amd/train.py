@@ -34,12 +34,14 @@ if __package__ in (None, ""):  # executed as a file
     _pkg = importlib.import_module("plotpointe-gat-recommendation_amd")
     data, evaluation, model_mod = _pkg.data, importlib.import_module(_pkg.__name__ + ".evaluation"), _pkg.model
     sampler_mod, lightgcn_mod, optim_mod = _pkg.sampler, _pkg.lightgcn, _pkg.optim
+    neighbors_mod = _pkg.neighbors
 else:
     from . import data, evaluation
     from . import model as model_mod
     from . import sampler as sampler_mod
     from . import lightgcn as lightgcn_mod
     from . import optim as optim_mod
+    from . import neighbors as neighbors_mod
 
 
 def set_seed(seed: int):
@@ -210,6 +212,27 @@ def check_softmax_loss(args):
         raise ValueError("--negatives must be >= 1")
     if not (args.temperature > 0 and args.temperature != float("inf")):
         raise ValueError("--temperature must be finite and > 0")
+
+
+def check_fanout(args):
+    """--fanout F > 0 (fan-out neighbour sampling, neighbors.NeighborSampler): the GAT families on
+    one GPU only; F and --fanout-items within the sampler's range, --resample-every >= 1."""
+    if args.fanout == 0:
+        if args.fanout_items is not None:
+            raise ValueError("--fanout-items needs --fanout")
+        return
+    if args.model_family == "lightgcn":
+        raise NotImplementedError("--fanout with --model-family lightgcn is not implemented: LightGCN's adjacency "
+                                  "values are degree-normalised, so sampling the graph changes them")
+    if args.world_size > 1:
+        raise NotImplementedError(f"--fanout with --world-size {args.world_size} is not implemented: the sharded "
+                                  "trainers partition the whole graph once (--world-size 1)")
+    if not 1 <= args.fanout <= neighbors_mod.MAX_FANOUT:
+        raise ValueError(f"--fanout {args.fanout}: expected 1..{neighbors_mod.MAX_FANOUT} (0 = off)")
+    if args.fanout_items is not None and not 0 <= args.fanout_items <= neighbors_mod.MAX_FANOUT:
+        raise ValueError(f"--fanout-items {args.fanout_items}: expected 0..{neighbors_mod.MAX_FANOUT}")
+    if args.resample_every < 1:
+        raise ValueError("--resample-every must be >= 1")
 
 
 def check_negative_sampling(args) -> bool:
@@ -569,6 +592,14 @@ def build_parser():
                     help="after training, write every user's --attention-k most-attended items of the last layer "
                          "(ppgat_attention_topk) to this .npz; one GPU, GAT families only")
     ap.add_argument("--attention-k", type=int, default=10)
+    ap.add_argument("--fanout", type=int, default=0, metavar="F",
+                    help="train each epoch on a sampled graph: at most F in-neighbours per destination, drawn "
+                         "uniformly without replacement on the GPU (1..64; 0 = off, the whole graph).  Evaluation "
+                         "and the exports keep the whole graph.  GAT families, one GPU")
+    ap.add_argument("--fanout-items", type=int, default=None, metavar="F2",
+                    help="--fanout: the cap of the item destinations instead of F (0..64)")
+    ap.add_argument("--resample-every", type=int, default=1, metavar="K",
+                    help="--fanout: draw a new sampled graph every K epochs")
     return ap
 
 
@@ -576,6 +607,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     check_edge_features(args)
     check_softmax_loss(args)
+    check_fanout(args)
     logq = check_negative_sampling(args)
     if args.recommend_out and args.world_size > 1:
         raise NotImplementedError("--recommend-out runs on one GPU (--world-size 1): the lists are made from the "
@@ -676,8 +708,20 @@ def main(argv=None):
             weights = sampler_mod.BPRSampler.popularity_weights(ptr, flat, n_items, cfg.popularity_power)
         dev_sampler = sampler_mod.BPRSampler(ptr, flat, n_items, device=device, item_weights=weights)
     ssm_corr = dev_sampler.correction(cfg.negatives) if logq and args.shared_negatives == 0 else None
+    nb_sampler = None
+    if args.fanout > 0:  # one GPU (refused above otherwise)
+        fanout_of = None
+        if args.fanout_items is not None:  # users keep --fanout (-1 would keep all), items take F2
+            fanout_of = torch.full((n_users + n_items,), args.fanout, dtype=torch.int32, device=device)
+            fanout_of[n_users:] = args.fanout_items
+        nb_sampler = neighbors_mod.NeighborSampler(edge_index, n_users + n_items, args.fanout, seed=cfg.seed,
+                                                   fanout_of=fanout_of)
+    step_edges, step_attr = edge_index, edge_attr
     for epoch in range(1, cfg.epochs + 1):
         model.train()
+        if nb_sampler is not None and (epoch - 1) % args.resample_every == 0:
+            step_edges, eid, _ = nb_sampler.epoch(epoch - 1)
+            step_attr = edge_attr.index_select(0, eid) if edge_attr is not None else None
         if args.fast_sampler:
             u, i, j = dev_sampler.sample(cfg.samples_per_epoch, seed=cfg.seed,
                                          offset=(epoch - 1) * cfg.samples_per_epoch)
@@ -697,8 +741,8 @@ def main(argv=None):
                 softmax = (dev_sampler.train_candidates(u, i, cfg.negatives, seed=cfg.seed + epoch), cfg.temperature)
                 if logq:
                     softmax += (ssm_corr,)
-            loss_val = float(epoch_step(model, opt, item_feats, edge_index, n_users, u, i, j, cfg.loss,
-                                        edge_attr=edge_attr, softmax=softmax, shared=shared).item())
+            loss_val = float(epoch_step(model, opt, item_feats, step_edges, n_users, u, i, j, cfg.loss,
+                                        edge_attr=step_attr, softmax=softmax, shared=shared).item())
         else:
             # each rank: its own users' triples (the sum over ranks is the reference's mean),
             # dense gradients all-reduced, user rows updated by their owner
@@ -721,7 +765,8 @@ def main(argv=None):
         if lead:
             print(f"[{tag}][Epoch {epoch}] val: {val_metrics}")
         if args.structured_logs and lead:
-            log_event("epoch_end", run_id=run_id, epoch=epoch, loss=loss_val, val=val_metrics)
+            sampled = {"sampled_edges": int(step_edges.size(1))} if nb_sampler is not None else {}
+            log_event("epoch_end", run_id=run_id, epoch=epoch, loss=loss_val, val=val_metrics, **sampled)
         if val_metrics.get("ndcg@20", 0.0) > best:
             best = val_metrics.get("ndcg@20", 0.0)
             sd = model.state_dict() if sharded is None else sharded.full_state_dict()  # collective when sharded
