@@ -15,6 +15,9 @@
 
 namespace ppgat {
 
+// an index input brought into [0, n): the product library clamps, the debug library refuses first
+__device__ __forceinline__ int64_t clamp_idx(int64_t v, int64_t n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
+
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 __device__ __forceinline__ float4 f4(float a) { return make_float4(a, a, a, a); }

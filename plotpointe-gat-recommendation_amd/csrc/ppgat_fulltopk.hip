@@ -4,13 +4,13 @@
 //   s(i) = <U[u], I[i]>;  out[b, 0..k) = the first k of { i not in history(u) } under the total
 //   order (s descending, i ascending); fewer than k eligible items: the tail is -1 / -inf
 //
-// The product engine is k_full_rank's (ppgat_fullrank.hip), restated here so that kernel's
-// registers and schedule stay exactly as measured: a block owns TM queries (32 per wave), keeps
-// their user rows as split bf16 B fragments in registers, walks the item table in ascending TN-item
-// tiles (loaded once per block, split once, double buffered in LDS with the XOR swizzle), builds the
-// history mask per tile from a sorted cursor, and takes the 32x32x16 product transposed, so a lane
-// holds 16 scores of ONE user.  The six-term chain, its k order and the fp32 accumulation are the
-// same, so a (user, item) score here is bitwise the score k_full_rank compares.
+// The product is the score-tile engine of ppgat_score_tile.h, the one k_full_rank
+// (ppgat_fullrank.hip) uses, with that kernel's geometry: a block owns TM queries (32 per wave),
+// keeps their user rows as split bf16 B fragments in registers, walks the item table in ascending
+// TN-item tiles, builds the history mask per tile from a sorted cursor, and takes the 32x32x16
+// product transposed, so a lane holds 16 scores of ONE user.  Fragments, staging, the six-term
+// chain and its k order are the same code, so a (user, item) score here is bitwise the score
+// k_full_rank compares.  The tile loop and the selection epilogue are this file's own.
 //
 // Selection epilogue.  The lane's user has a threshold thr (the k-th best score kept so far, -inf
 // until k items are kept; both lanes of a user read it from LDS).  A non-masked score passes when
@@ -39,14 +39,14 @@
 #include <stdint.h>
 
 #include "ppgat_internal.h"
-#include "ppgat_split.h"
+#include "ppgat_device.h"
+#include "ppgat_score_tile.h"
 
 namespace ppgat {
 namespace {
 
 using split::f32x16;
 using split::mfma32_x6;
-using split::split3;
 using split::u32x4;
 
 constexpr int kFtMaxK = 128;
@@ -54,8 +54,6 @@ constexpr int kFtMaxCap = 192;  // ft_cap(kFtMaxK)
 constexpr int kFtPerLane = 3;   // ceil(kFtMaxCap / 64)
 constexpr int kFtEarly = 16;    // appended entries from which a user joins a block-wide compaction round
 
-__device__ __forceinline__ float4 ft_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ int64_t ft_clamp(int64_t v, int64_t n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
 // candidate a = (score bits, item) comes before b under (score descending, item ascending)
 __device__ __forceinline__ bool ft_beats(float as, uint32_t ai, float bs, uint32_t bi) {
   return as > bs || (as == bs && ai < bi);
@@ -65,29 +63,19 @@ __device__ __forceinline__ void ft_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ
 // keeps the compiler from moving accesses across it
 __device__ __forceinline__ void ft_fence_wave() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); }
 
+// k_full_rank's choice: 8 waves (C = 256: 4, one wave per SIMD); 128, 128, 64, 32 items per tile
 template <int C>
-struct FtCfg {
-  static constexpr int WAVES = C == 256 ? 4 : 8;       // C = 256: 192 VGPRs of user fragments, one wave per SIMD
-  static constexpr int NT = 64 * WAVES;                // threads
-  static constexpr int TM = 32 * WAVES;                // queries per block
-  static constexpr int TN = C >= 64 ? 8192 / C : 128;  // items per tile: 128, 128, 64, 32
-  static constexpr int SUB = TN / 32;                  // 32-item subtiles (mask words per query)
-  static constexpr int CPR = C / 8;                    // 16-byte (8 x bf16) units per row
-  static constexpr int UPT = TN * CPR / NT;            // units staged per thread: 1, 2, 2, 4
-  static constexpr int ROWB = 2 * C;                   // bytes per staged row
-  static constexpr int PART = TN * ROWB;               // bytes per split term
-  static constexpr int BUF = 3 * PART;                 // one staged tile
-  static constexpr int KS = C / 16;                    // k steps of the 32x32x16 MFMA
-  static constexpr size_t OFF_MASK = 2 * (size_t)BUF;                    // [2][TM][SUB] u32
-  static constexpr size_t OFF_CNT = OFF_MASK + 2 * (size_t)TM * SUB * 4;  // [TM] i32
-  static constexpr size_t OFF_THR = OFF_CNT + (size_t)TM * 4;             // [TM] f32
-  static constexpr size_t OFF_NS = OFF_THR + (size_t)TM * 4;              // [TM] i32
-  static constexpr size_t OFF_STAGE = OFF_NS + (size_t)TM * 4;            // [WAVES][kFtMaxCap] uint2
-  static constexpr size_t OFF_FLAG = OFF_STAGE + (size_t)WAVES * kFtMaxCap * 8;  // [2] i32
+using FtGeo = score::Geo<C, (C == 256 ? 4 : 8), (C >= 64 ? 8192 / C : 128)>;
+template <int C>
+struct FtCfg : FtGeo<C> {
+  using G = FtGeo<C>;
+  static constexpr size_t OFF_MASK = 2 * (size_t)G::BUF;                       // [2][TM][SUB] u32
+  static constexpr size_t OFF_CNT = OFF_MASK + 2 * (size_t)G::TM * G::SUB * 4;  // [TM] i32
+  static constexpr size_t OFF_THR = OFF_CNT + (size_t)G::TM * 4;                // [TM] f32
+  static constexpr size_t OFF_NS = OFF_THR + (size_t)G::TM * 4;                 // [TM] i32
+  static constexpr size_t OFF_STAGE = OFF_NS + (size_t)G::TM * 4;               // [WAVES][kFtMaxCap] uint2
+  static constexpr size_t OFF_FLAG = OFF_STAGE + (size_t)G::WAVES * kFtMaxCap * 8;  // [2] i32
   static constexpr size_t LDS = OFF_FLAG + 16;
-  __host__ __device__ static constexpr int swz(int row) {  // as FrCfg::swz
-    return CPR >= 16 ? (row & 15) : ((row / (16 / CPR)) & (CPR - 1));
-  }
 };
 
 struct FtArg {
@@ -105,8 +93,6 @@ struct FtArg {
   int64_t tiles_per_split;
   int k, cap;
 };
-
-constexpr int64_t kFtNoItem = INT64_MAX;
 
 template <int C>
 __global__ void __launch_bounds__(FtCfg<C>::NT, 1) k_full_topk(FtArg a) {
@@ -132,84 +118,33 @@ __global__ void __launch_bounds__(FtCfg<C>::NT, 1) k_full_topk(FtArg a) {
   const int wu = wave * 32 + r;
   const int64_t b = (int64_t)blockIdx.x * F::TM + wu;
   const int64_t bc = b < a.n_query ? b : a.n_query - 1;
-  const int64_t u = ft_clamp(a.users ? a.users[bc] : bc, a.n_users);
+  const int64_t u = clamp_idx(a.users ? a.users[bc] : bc, a.n_users);
   u32x4 ub[F::KS][3];
-  {
-    const float* up = a.U + u * a.ldu + 8 * hf;
-#pragma unroll
-    for (int ks = 0; ks < F::KS; ++ks) split3(ft_ld4(up + 16 * ks), ft_ld4(up + 16 * ks + 4), ub[ks][0], ub[ks][1], ub[ks][2]);
-  }
+  score::load_owned<F>(a.U + u * a.ldu, hf, ub);
   // the block's candidate buffers: one of cap entries per query slot (b < slots always)
   uint2* const cblk = a.cand + ((int64_t)blockIdx.y * a.slots + (int64_t)blockIdx.x * F::TM) * cap;
   uint2* const cmine = cblk + (int64_t)wu * cap;
 
   // ---- the exclusion cursor of query tid (threads 0 .. TM-1) ----
-  int64_t cur = 0, cend = 0;
+  score::HistCursor cursor;
   if (tid < F::TM) {
     sCnt[tid] = 0;
     sThr[tid] = -INFINITY;
     sNs[tid] = 0;
     if (tid < 2) sFlag[tid] = 0;
     const int64_t be = (int64_t)blockIdx.x * F::TM + tid;
-    if (be < a.n_query && a.uptr) {
-      const int64_t ue = ft_clamp(a.users ? a.users[be] : be, a.n_users);
-      cur = a.uptr[ue];
-      cend = a.uptr[ue + 1];
-      if (jlo > 0) {  // first history item >= jlo
-        int64_t lo = cur, hi = cend;
-        while (lo < hi) {
-          const int64_t mid = lo + ((hi - lo) >> 1);
-          if (a.hist[mid] < jlo) lo = mid + 1; else hi = mid;
-        }
-        cur = lo;
-      }
-    }
+    if (be < a.n_query && a.uptr) cursor.seek(a.uptr, a.hist, clamp_idx(a.users ? a.users[be] : be, a.n_users), jlo);
   }
-  int64_t nxt = cur < cend ? (int64_t)a.hist[cur] : kFtNoItem;
-
+  cursor.start(a.hist);
   auto build_mask = [&](int64_t t, int bufi) {
-    if (tid < F::TM) {
-      const int64_t j0 = t * F::TN, jend = j0 + F::TN;
-      uint32_t* w = sMask + ((size_t)bufi * F::TM + tid) * F::SUB;
-      const int64_t valid = jhi - j0;  // >= 1; columns past it are outside the item range
-#pragma unroll
-      for (int s = 0; s < F::SUB; ++s) {
-        const int64_t v = valid - 32 * s;
-        w[s] = v >= 32 ? 0u : (v <= 0 ? 0xffffffffu : (0xffffffffu << (int)v));
-      }
-      while (nxt < jend) {
-        const int64_t d = nxt - j0;
-        if (d >= 0) w[d >> 5] |= 1u << (int)(d & 31);
-        ++cur;
-        nxt = cur < cend ? (int64_t)a.hist[cur] : kFtNoItem;
-      }
-    }
+    if (tid < F::TM) score::mask_words<F>(sMask + ((size_t)bufi * F::TM + tid) * F::SUB, t * F::TN, jhi, cursor, a.hist);
   };
 
   float4 pf[F::UPT][2];
   auto load_tile = [&](int64_t t) {
-#pragma unroll
-    for (int kk = 0; kk < F::UPT; ++kk) {
-      const int e = tid + kk * F::NT, row = e / F::CPR, ch = e % F::CPR;
-      int64_t j = t * F::TN + row;
-      j = j < n_items ? j : n_items - 1;
-      const float* src = a.I + j * ldi + 8 * ch;
-      pf[kk][0] = ft_ld4(src);
-      pf[kk][1] = ft_ld4(src + 4);
-    }
+    score::tile_load<F>(pf, t, n_items, tid, [&](int64_t j) { return a.I + j * ldi; });
   };
-  auto store_tile = [&](int bufi) {
-#pragma unroll
-    for (int kk = 0; kk < F::UPT; ++kk) {
-      const int e = tid + kk * F::NT, row = e / F::CPR, ch = e % F::CPR;
-      u32x4 h, m, l;
-      split3(pf[kk][0], pf[kk][1], h, m, l);
-      unsigned char* dst = ft_lds + bufi * F::BUF + row * F::ROWB + ((ch ^ F::swz(row)) << 4);
-      *reinterpret_cast<u32x4*>(dst) = h;
-      *reinterpret_cast<u32x4*>(dst + F::PART) = m;
-      *reinterpret_cast<u32x4*>(dst + 2 * F::PART) = l;
-    }
-  };
+  auto store_tile = [&](int bufi) { score::tile_store<F>(ft_lds + bufi * F::BUF, pf, tid); };
 
   // Compaction of user column ur of this wave (wave-uniform; all 64 lanes take part).  The buffer
   // holds ns entries in order (what the last compaction kept) and n - ns appended since.  All n are
@@ -280,8 +215,7 @@ __global__ void __launch_bounds__(FtCfg<C>::NT, 1) k_full_topk(FtArg a) {
 
   float thr = -INFINITY;
   int cnt = 0;  // entries in the user's buffer: the same number in the user's two lanes
-  // unit 2 ks + hf of row r, swizzled: ((2 ks) ^ hf ^ swz) << 4 = (32 ks) ^ xoff
-  const int xoff = (hf ^ F::swz(r)) << 4;
+  const int xoff = F::xoff(r, hf);
   for (int64_t t = t0; t < t1; ++t) {
     const int bufi = (int)((t - t0) & 1);
     if (t + 1 < t1) load_tile(t + 1);
@@ -305,15 +239,9 @@ __global__ void __launch_bounds__(FtCfg<C>::NT, 1) k_full_topk(FtArg a) {
         cnt = *reinterpret_cast<volatile int*>(sCnt + wu);
       }
     }
-    const unsigned char* tile = ft_lds + bufi * F::BUF + r * F::ROWB;
-    auto read_a = [&](int idx, u32x4 (&f)[3]) {
-      const unsigned char* pa = tile + (idx / F::KS) * 32 * F::ROWB + ((32 * (idx % F::KS)) ^ xoff);
-      f[0] = *reinterpret_cast<const u32x4*>(pa);
-      f[1] = *reinterpret_cast<const u32x4*>(pa + F::PART);
-      f[2] = *reinterpret_cast<const u32x4*>(pa + 2 * F::PART);
-    };
+    const unsigned char* tile_r = ft_lds + bufi * F::BUF + r * F::ROWB;
     u32x4 fa[3];
-    read_a(0, fa);
+    score::read_a<F>(tile_r, 0, xoff, fa);
     f32x16 acc;
     // k_full_rank's flat (subtile, k step) sequence -- the next step's three A units read from LDS
     // while the current step's six MFMAs run, across the subtile boundary too -- written as two
@@ -326,7 +254,7 @@ __global__ void __launch_bounds__(FtCfg<C>::NT, 1) k_full_topk(FtArg a) {
       for (int ks = 0; ks < F::KS; ++ks) {
         const int idx = sb * F::KS + ks;
         u32x4 fn[3];
-        if (idx + 1 < F::SUB * F::KS) read_a(idx + 1, fn);
+        if (idx + 1 < F::SUB * F::KS) score::read_a<F>(tile_r, idx + 1, xoff, fn);
         acc = mfma32_x6(fa, ub[ks], acc);
         __builtin_amdgcn_sched_barrier(0);
         if (idx + 1 < F::SUB * F::KS) {
@@ -335,7 +263,7 @@ __global__ void __launch_bounds__(FtCfg<C>::NT, 1) k_full_topk(FtArg a) {
           fa[2] = fn[2];
         }
       }
-      // accumulator q of lane (r, hf) is item row (q & 3) + 8 (q >> 2) + 4 hf of user column r
+      // accumulator q of lane (r, hf) is item row acc_row(q) + 4 hf of user column r
       const uint32_t m = sMask[((size_t)bufi * F::TM + wu) * F::SUB + sb] >> (4 * hf);
       // the 16 pass predicates as wave masks (one compare each, the rest is scalar work); their
       // union decides the branch
@@ -350,7 +278,7 @@ __global__ void __launch_bounds__(FtCfg<C>::NT, 1) k_full_topk(FtArg a) {
         anyq = 0;
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-          bq[q] &= __builtin_amdgcn_ballot_w64(((m >> ((q & 3) + 8 * (q >> 2))) & 1u) == 0u);
+          bq[q] &= __builtin_amdgcn_ballot_w64(((m >> score::acc_row(q)) & 1u) == 0u);
           anyq |= bq[q];
         }
         if (anyq == 0) continue;
@@ -374,7 +302,9 @@ __global__ void __launch_bounds__(FtCfg<C>::NT, 1) k_full_topk(FtArg a) {
       }
       // One accumulator register at a time, skipped when no lane passes in it (the usual case).  The
       // user's two lanes hold the same cnt and see each other's bit in the mask: hf = 0 takes slot
-      // cnt, hf = 1 the one after it if both pass -- no atomic is needed.
+      // cnt, hf = 1 the one after it if both pass -- no atomic is needed.  (The item's row is
+      // score::acc_row(q), kept as two summands: folded into one constant it compiles to 31-62 fewer
+      // VGPRs at C <= 128 and to another nominal occupancy, a change to make with a measurement.)
       const int item0 = (int)(t * F::TN) + 32 * sb + 4 * hf;
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
@@ -455,14 +385,10 @@ FtPlan ft_plan(int64_t n_query, int64_t n_items, int k, int ncu) {
   using F = FtCfg<C>;
   FtPlan p;
   p.utiles = (n_query + F::TM - 1) / F::TM;
-  const int64_t ntiles = (n_items + F::TN - 1) / F::TN;
-  p.nsplit = 1;
-  if (p.utiles > 0 && p.utiles < ncu) {  // too few query tiles to fill the chip: split the item range
-    p.nsplit = (ncu + p.utiles - 1) / p.utiles;
-    if (p.nsplit > ntiles) p.nsplit = ntiles;
-  }
-  p.tiles_per_split = (ntiles + p.nsplit - 1) / p.nsplit;
-  p.nsplit = (ntiles + p.tiles_per_split - 1) / p.tiles_per_split;  // every split non-empty
+  // too few query tiles to fill the chip: the item range is split
+  const score::ItemSplit sp = score::split_items(p.utiles, (n_items + F::TN - 1) / F::TN, ncu);
+  p.nsplit = sp.nsplit;
+  p.tiles_per_split = sp.tiles_per_split;
   p.slots = p.utiles * F::TM;
   p.cap = ft_cap(k);
   p.cnt_off = (size_t)p.nsplit * p.slots * p.cap * sizeof(uint2);
@@ -477,13 +403,6 @@ FtPlan ft_plan_any(int C, int64_t n_query, int64_t n_items, int k, int ncu) {
     case 128: return ft_plan<128>(n_query, n_items, k, ncu);
     default: return ft_plan<256>(n_query, n_items, k, ncu);
   }
-}
-
-hipError_t ft_ncu(int* ncu) {
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  return hipDeviceGetAttribute(ncu, hipDeviceAttributeMultiprocessorCount, dev);
 }
 
 template <int C>
@@ -510,7 +429,7 @@ hipError_t full_topk_workspace(int64_t n_query, int64_t n_items, int C, int k, s
   *bytes = 0;
   if (n_query == 0) return hipSuccess;
   int ncu = 0;
-  const hipError_t e = ft_ncu(&ncu);
+  const hipError_t e = score::cu_count(&ncu);
   if (e != hipSuccess) return e;
   *bytes = ft_plan_any(C, n_query, n_items, k, ncu).bytes;
   return hipSuccess;
@@ -522,7 +441,7 @@ hipError_t full_topk(const float* U, int64_t ldu, int64_t n_users, const float* 
   if (n_query == 0) return hipSuccess;
   if (n_query > 0x7fffffff) return hipErrorInvalidValue;  // one merge block per query
   int ncu = 0;
-  hipError_t e = ft_ncu(&ncu);
+  hipError_t e = score::cu_count(&ncu);
   if (e != hipSuccess) return e;
   const FtPlan p = ft_plan_any(C, n_query, n_items, k, ncu);
   if (!ws || ws_bytes < p.bytes) return hipErrorInvalidValue;

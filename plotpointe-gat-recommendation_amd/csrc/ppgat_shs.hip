@@ -9,10 +9,13 @@
 //
 // The [S, P] scores are a product of gathered rows on v_mfma_f32_32x32x16_bf16 with the
 // three-term split of ppgat_split.h (fp32 accuracy) and are never written.  One kernel, k_shs,
-// serves the three sweeps.  A block "owns" 128 rows (32 per wave) whose split fragments stay in
-// registers as the B operand, and "streams" the other side's gathered rows through double-buffered
-// LDS tiles as the A operand, so the streamed row sits on the accumulator's row and the owned row
-// on the lane:
+// serves the three sweeps on the score-tile engine of ppgat_score_tile.h (shared with the
+// full-catalogue rank and top-K kernels: geometry and swizzle, owned fragments, tile staging, the
+// A-fragment read, the diagonal score).  A block "owns" 128 rows (32 per wave) whose split
+// fragments stay in registers as the B operand, and "streams" the other side's gathered rows
+// through double-buffered LDS tiles as the A operand, so the streamed row sits on the
+// accumulator's row and the owned row on the lane.  The sweeps' loops, their second product and
+// the lse / mask / correction staging beside the tile are this file's own:
 //   FWD       owns samples (rows Z[u_t]), streams the pool.  Epilogue: an online (max, sum) per
 //             lane over the unmasked scores; the two lane halves merge with the symmetric rule of
 //             the sampled loss.  A launch with few sample tiles splits the pool range over
@@ -49,7 +52,7 @@
 #include <math.h>
 
 #include "ppgat_internal.h"
-#include "ppgat_split.h"
+#include "ppgat_score_tile.h"  // before the pragma, as ppgat_split.h was: it has no chain to contract
 
 #pragma clang fp contract(off)
 
@@ -71,8 +74,6 @@ unsigned sh_key_bits(int64_t n) {
   return b;
 }
 
-__device__ __forceinline__ int64_t sh_clamp(int64_t v, int64_t n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
-
 // (m, l) <- (m, l) merged with (mo, lo); symmetric in its two states, -inf marks an empty one
 __device__ __forceinline__ void sh_merge(float& m, float& l, float mo, float lo) {
   const float mn = fmaxf(m, mo);
@@ -86,29 +87,18 @@ enum { SH_FWD = 0, SH_USER = 1, SH_ITEM = 2 };
 constexpr int kShFill = 256;    // blocks wanted before a sweep stops splitting its streamed range
 constexpr int kShMinTiles = 4;  // streamed tiles a split holds at least
 
+// 4 waves, one per SIMD (the backward's accumulators need the file); 128 (C = 64) or 64 (C = 128)
+// streamed rows per tile, 4 units staged per thread
 template <int C>
-struct ShCfg {
-  static constexpr int WAVES = 4;                 // one wave per SIMD: the backward's accumulators need the file
-  static constexpr int NT = 64 * WAVES;           // threads
-  static constexpr int TM = 32 * WAVES;           // owned rows per block
-  static constexpr int TN = 8192 / C;             // streamed rows per tile: 128 (C = 64), 64 (C = 128)
-  static constexpr int SUB = TN / 32;             // 32-row subtiles
-  static constexpr int CPR = C / 8;               // 16-byte (8 x bf16) units per row
-  static constexpr int UPT = TN * CPR / NT;       // units staged per thread: 4
-  static constexpr int ROWB = 2 * C;              // bytes per staged row
-  static constexpr int PART = TN * ROWB;          // bytes per split term
-  static constexpr int BUF = 3 * PART;            // one staged tile
-  static constexpr int KS = C / 16;               // k steps of the first product
-  static constexpr int CB = C / 32;               // 32-channel blocks of the second product
-  static constexpr int MPT = TN * WAVES / NT;     // streamed mask words staged per thread (ITEM)
-  static constexpr size_t LDS = 2 * (size_t)BUF + 2 * (size_t)TN * 4 + 2 * (size_t)TN * WAVES * 4;
+using ShTile = score::Geo<C, 4, 8192 / C>;
+template <int C>
+struct ShCfg : ShTile<C> {
+  using G = ShTile<C>;
+  static constexpr int CB = C / 32;                     // 32-channel blocks of the second product
+  static constexpr int MPT = G::TN * G::WAVES / G::NT;  // streamed mask words staged per thread (ITEM)
+  static constexpr size_t LDS = 2 * (size_t)G::BUF + 2 * (size_t)G::TN * 4 + 2 * (size_t)G::TN * G::WAVES * 4;
   static_assert(C == 64 || C == 128, "shs: C in {64, 128}");
-  static_assert(TN <= NT && UPT * NT == TN * CPR && MPT * NT == TN * WAVES, "shs: staging covers the tile");
-  // the bank swizzle of ppgat_fullrank.hip: XOR the unit index with the row's position among
-  // 16 rows (256-byte rows) or among the lines when two rows share one (C = 64)
-  __host__ __device__ static constexpr int swz(int row) {
-    return CPR >= 16 ? (row & 15) : ((row / (16 / CPR)) & (CPR - 1));
-  }
+  static_assert(G::TN <= G::NT && MPT * G::NT == G::TN * G::WAVES, "shs: staging covers the tile");
 };
 
 struct ShArg {
@@ -157,40 +147,20 @@ __global__ void __launch_bounds__(ShCfg<C>::NT, 1) k_shs(ShArg a) {
   const int64_t t1 = t0 + a.tiles_per_split < ntiles ? t0 + a.tiles_per_split : ntiles;
 
   auto owned_row = [&](int64_t i) -> const float* {
-    return ITEM ? a.Z + (a.n_users + sh_clamp(a.pool[i], a.n_items)) * C : a.Z + sh_clamp(a.u[i], a.n_users) * C;
+    return ITEM ? a.Z + (a.n_users + clamp_idx(a.pool[i], a.n_items)) * C : a.Z + clamp_idx(a.u[i], a.n_users) * C;
   };
   auto streamed_row = [&](int64_t i) -> const float* {
-    return ITEM ? a.Z + sh_clamp(a.u[i], a.n_users) * C : a.Z + (a.n_users + sh_clamp(a.pool[i], a.n_items)) * C;
+    return ITEM ? a.Z + clamp_idx(a.u[i], a.n_users) * C : a.Z + (a.n_users + clamp_idx(a.pool[i], a.n_items)) * C;
   };
 
   // ---- this lane's owned row: column r of the wave's 32; rows past NO repeat the last ----
   const int64_t b = (int64_t)blockIdx.x * F::TM + wave * 32 + r;
   const int64_t bc = b < NO ? b : NO - 1;
   u32x4 ub[F::KS][3];
-  {
-    const float* up = owned_row(bc) + 8 * hf;
-#pragma unroll
-    for (int ks = 0; ks < F::KS; ++ks) split3(ld4(up + 16 * ks), ld4(up + 16 * ks + 4), ub[ks][0], ub[ks][1], ub[ks][2]);
-  }
+  score::load_owned<F>(owned_row(bc), hf, ub);
   // ---- FWD, first split: s0, the users against their own positives' rows, the diagonal ----
   if (MODE == SH_FWD && blockIdx.y == 0) {
-    f32x16 acc;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc[q] = 0.f;
-    const float* pp = a.Z + (a.n_users + sh_clamp(a.pos[bc], a.n_items)) * C + 8 * hf;
-#pragma unroll
-    for (int ks = 0; ks < F::KS; ++ks) {
-      u32x4 ia[3];
-      split3(ld4(pp + 16 * ks), ld4(pp + 16 * ks + 4), ia[0], ia[1], ia[2]);
-      acc = mfma32_x6(ia, ub[ks], acc);
-    }
-    // accumulator q of lane (r, hf) is streamed row (q & 3) + 8 (q >> 2) + 4 hf of owned column r
-    const int qsel = (r & 3) + 4 * (r >> 3);
-    float v = 0.f;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) v = q == qsel ? acc[q] : v;
-    const float vo = __shfl_xor(v, 32);
-    const float sp = hf == ((r >> 2) & 1) ? v : vo;
+    const float sp = score::diag_score<F>(a.Z + (a.n_users + clamp_idx(a.pos[bc], a.n_items)) * C, ub, r, hf);
     if (hf == 0 && b < NO) a.s0[b] = sp * a.inv_tau;
   }
   const float lse_own = MODE == SH_USER ? a.lse[bc] : 0.f;
@@ -200,15 +170,7 @@ __global__ void __launch_bounds__(ShCfg<C>::NT, 1) k_shs(ShArg a) {
   float pf_lse = 0.f;
   uint32_t pf_msk[F::MPT];
   auto load_tile = [&](int64_t t) {
-#pragma unroll
-    for (int k = 0; k < F::UPT; ++k) {
-      const int e = tid + k * F::NT, row = e / F::CPR, ch = e % F::CPR;
-      int64_t j = t * F::TN + row;
-      j = j < NS ? j : NS - 1;
-      const float* src = streamed_row(j) + 8 * ch;
-      pf[k][0] = ld4(src);
-      pf[k][1] = ld4(src + 4);
-    }
+    score::tile_load<F>(pf, t, NS, tid, streamed_row);
     if (ITEM) {
       if (tid < F::TN) {
         const int64_t j = t * F::TN + tid;
@@ -228,16 +190,7 @@ __global__ void __launch_bounds__(ShCfg<C>::NT, 1) k_shs(ShArg a) {
     }
   };
   auto store_tile = [&](int bufi) {
-#pragma unroll
-    for (int k = 0; k < F::UPT; ++k) {
-      const int e = tid + k * F::NT, row = e / F::CPR, ch = e % F::CPR;
-      u32x4 h, m, l;
-      split3(pf[k][0], pf[k][1], h, m, l);
-      unsigned char* dst = sh_lds + bufi * F::BUF + row * F::ROWB + ((ch ^ F::swz(row)) << 4);
-      *reinterpret_cast<u32x4*>(dst) = h;
-      *reinterpret_cast<u32x4*>(dst + F::PART) = m;
-      *reinterpret_cast<u32x4*>(dst + 2 * F::PART) = l;
-    }
+    score::tile_store<F>(sh_lds + bufi * F::BUF, pf, tid);
     if (ITEM) {
       if (tid < F::TN) sLse[bufi * F::TN + tid] = pf_lse;
 #pragma unroll
@@ -259,8 +212,7 @@ __global__ void __launch_bounds__(ShCfg<C>::NT, 1) k_shs(ShArg a) {
 #pragma unroll
       for (int q = 0; q < 16; ++q) acc2[cb][q] = 0.f;
   }
-  // unit 2 ks + hf of row r, swizzled: ((2 ks) ^ hf ^ swz) << 4 = (32 ks) ^ xoff  (swz(32 sb + r) = swz(r))
-  const int xoff = (hf ^ F::swz(r)) << 4;
+  const int xoff = F::xoff(r, hf);
   for (int64_t t = t0; t < t1; ++t) {
     const int bufi = (int)((t - t0) & 1);
     uint32_t mw[F::SUB];  // FWD / USER: this owned row's mask words of the tile (words past W: all masked)
@@ -280,14 +232,11 @@ __global__ void __launch_bounds__(ShCfg<C>::NT, 1) k_shs(ShArg a) {
       for (int q = 0; q < 16; ++q) acc[q] = 0.f;
 #pragma unroll
       for (int ks = 0; ks < F::KS; ++ks) {
-        const unsigned char* pa = tile + (32 * sb + r) * F::ROWB + ((32 * ks) ^ xoff);
         u32x4 fa[3];
-        fa[0] = *reinterpret_cast<const u32x4*>(pa);
-        fa[1] = *reinterpret_cast<const u32x4*>(pa + F::PART);
-        fa[2] = *reinterpret_cast<const u32x4*>(pa + 2 * F::PART);
+        score::read_a<F>(tile + r * F::ROWB, sb * F::KS + ks, xoff, fa);
         acc = mfma32_x6(fa, ub[ks], acc);
       }
-      // accumulator q: streamed row 32 sb + (q & 3) + 8 (q >> 2) + 4 hf, owned column r
+      // accumulator q: streamed row 32 sb + acc_row(q) + 4 hf, owned column r
       if (MODE == SH_FWD) {
         const uint32_t m = mw[sb] >> (4 * hf);
         const float* cs = sLse + bufi * F::TN + 32 * sb + 4 * hf;  // CORR: the streamed rows' corrections
@@ -295,7 +244,7 @@ __global__ void __launch_bounds__(ShCfg<C>::NT, 1) k_shs(ShArg a) {
         float tm = -INFINITY;
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-          const int row = (q & 3) + 8 * (q >> 2);
+          const int row = score::acc_row(q);
           const bool in = ((m >> row) & 1u) == 0u;
           const float lg = CORR ? acc[q] * a.inv_tau - cs[row] : acc[q] * a.inv_tau;
           sc[q] = in ? lg : -INFINITY;
@@ -316,7 +265,7 @@ __global__ void __launch_bounds__(ShCfg<C>::NT, 1) k_shs(ShArg a) {
           const uint32_t* ms = sMsk + (bufi * F::TN + 32 * sb + 4 * hf) * F::WAVES + wave;
 #pragma unroll
           for (int q = 0; q < 16; ++q) {
-            const int row = (q & 3) + 8 * (q >> 2);
+            const int row = score::acc_row(q);
             const bool in = ((ms[row * F::WAVES] >> r) & 1u) == 0u;
             const float lg = CORR ? acc[q] * a.inv_tau - corr_own : acc[q] * a.inv_tau;
             p[q] = in ? __expf(lg - ls[row]) : 0.f;
@@ -326,7 +275,7 @@ __global__ void __launch_bounds__(ShCfg<C>::NT, 1) k_shs(ShArg a) {
           const float* cs = sLse + bufi * F::TN + 32 * sb + 4 * hf;  // CORR: the streamed rows' corrections
 #pragma unroll
           for (int q = 0; q < 16; ++q) {
-            const int row = (q & 3) + 8 * (q >> 2);
+            const int row = score::acc_row(q);
             const bool in = ((m >> row) & 1u) == 0u;
             const float lg = CORR ? acc[q] * a.inv_tau - cs[row] : acc[q] * a.inv_tau;
             p[q] = in ? __expf(lg - lse_own) : 0.f;
@@ -373,7 +322,7 @@ __global__ void __launch_bounds__(ShCfg<C>::NT, 1) k_shs(ShArg a) {
       a.pl[(int64_t)blockIdx.y * a.S + b] = lsum;
     }
   } else if (b < NO) {
-    // acc2[cb][q]: channel 32 cb + (q & 3) + 8 (q >> 2) + 4 hf of owned row b
+    // acc2[cb][q]: channel 32 cb + acc_row(q) + 4 hf of owned row b
     const float g = a.grad_loss[0];
     const float sg = a.scale * g;
     float* out = a.G + ((int64_t)blockIdx.y * NO + b) * C + 4 * hf;
@@ -381,7 +330,7 @@ __global__ void __launch_bounds__(ShCfg<C>::NT, 1) k_shs(ShArg a) {
     const float* zp = a.Z;
     if (MODE == SH_USER) {  // the positive's term of the sample's gradient
       c0g = a.c0[b] * g;
-      zp = a.Z + (a.n_users + sh_clamp(a.pos[b], a.n_items)) * C + 4 * hf;
+      zp = a.Z + (a.n_users + clamp_idx(a.pos[b], a.n_items)) * C + 4 * hf;
     }
 #pragma unroll
     for (int cb = 0; cb < F::CB; ++cb)
@@ -439,11 +388,11 @@ __global__ void __launch_bounds__(256) k_shs_mask(const int64_t* __restrict__ u,
       }
       return lo;
     };
-    const int64_t pc = sh_clamp(p0, n_items);
+    const int64_t pc = clamp_idx(p0, n_items);
     const int64_t kp = lower(pc, 0);
     if (kp < P && pool[kp] == pc) w[kp >> 5] |= 1u << (int)(kp & 31);
     if (uptr != nullptr) {
-      const int64_t uc = sh_clamp(u0, n_users);
+      const int64_t uc = clamp_idx(u0, n_users);
       int64_t k = 0;  // the history ascends: the search window only moves forward
       for (int64_t cur = uptr[uc], cend = uptr[uc + 1]; cur < cend && k < P; ++cur) {
         const int64_t h = hist[cur];
@@ -460,7 +409,7 @@ __global__ void __launch_bounds__(256) k_shs_mask(const int64_t* __restrict__ u,
 __global__ void __launch_bounds__(256) k_shs_corr(const float* __restrict__ corr, const int64_t* __restrict__ pool,
                                                   int64_t P, int64_t n_items, float* __restrict__ corrp) {
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j < P) corrp[j] = corr[sh_clamp(pool[j], n_items)];
+  if (j < P) corrp[j] = corr[clamp_idx(pool[j], n_items)];
 }
 
 // ---------------------------------------------------------------------------
@@ -525,9 +474,9 @@ __global__ void k_shs_keys(const int64_t* __restrict__ u, const int64_t* __restr
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c * 16 < n_rows) *reinterpret_cast<uint4*>(touched + c * 16) = make_uint4(0u, 0u, 0u, 0u);
   if (c < S) {
-    ukey[c] = (int32_t)sh_clamp(u[c], n_users);
+    ukey[c] = (int32_t)clamp_idx(u[c], n_users);
     uval[c] = (int32_t)c;
-    ikey[c] = (int32_t)(n_users + sh_clamp(pos[c], n_items));
+    ikey[c] = (int32_t)(n_users + clamp_idx(pos[c], n_items));
     ival[c] = (int32_t)c;
   }
 }
@@ -554,7 +503,7 @@ __device__ __forceinline__ void sh_rec_load(const ShRecs& r, int64_t p, float g,
     src = t;
     cf = 1.f;
   } else {
-    src = (int32_t)sh_clamp(r.u[t], r.n_users);
+    src = (int32_t)clamp_idx(r.u[t], r.n_users);
     cf = r.c0[t] * g;
   }
 }
@@ -654,7 +603,7 @@ __global__ void __launch_bounds__(256) k_shs_pool_add(const float* __restrict__ 
   const int sg = threadIdx.x / LPR, sl = threadIdx.x % LPR;
   const int64_t j = (int64_t)blockIdx.x * SPB + sg;
   if (j >= P) return;
-  const int64_t row = n_users + sh_clamp(pool[j], n_items);
+  const int64_t row = n_users + clamp_idx(pool[j], n_items);
   float4 acc = ld4(Gp + j * C + sl * 4);
   for (int y = 1; y < nsplit; ++y) acc = add4(acc, ld4(Gp + ((int64_t)y * P + j) * C + sl * 4));
   if (touched[row]) acc = add4(acc, ld4(dZ + row * C + sl * 4));
@@ -664,7 +613,7 @@ __global__ void __launch_bounds__(256) k_shs_pool_add(const float* __restrict__ 
 __global__ void __launch_bounds__(256) k_shs_pool_mark(const int64_t* __restrict__ pool, int64_t P, int64_t n_users,
                                                        int64_t n_items, uint8_t* __restrict__ touched) {
   const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (j < P) touched[n_users + sh_clamp(pool[j], n_items)] = 1;
+  if (j < P) touched[n_users + clamp_idx(pool[j], n_items)] = 1;
 }
 
 // rows nothing reaches

@@ -54,8 +54,6 @@ unsigned key_bits(int64_t n) {
   return b;
 }
 
-__device__ __forceinline__ int64_t clamp_idx(int64_t v, int64_t n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
-
 template <int C>
 struct Geo {
   static constexpr int LPR = C / 4;                      // lanes per row

@@ -31,7 +31,6 @@ unsigned key_bits(int64_t n) {
   return b;
 }
 
-__device__ __forceinline__ int64_t clamp_idx(int64_t v, int64_t n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
 // Z row of node id v (users [0, n_users), items n_users + i); row_map != NULL remaps (sharded
 // runs keep Z in a padded per-rank row space)
 __device__ __forceinline__ int64_t zrow(const int32_t* row_map, int64_t v) { return row_map ? row_map[v] : v; }

@@ -24,6 +24,7 @@ HELPERS = {
     "ld4": "float4", "st4": "void", "f4": "float4", "fma4": "float4", "add4": "float4", "mul4": "float4",
     "dot4": "float", "comp": "float", "shfl_xor4": "float4", "absmax4": "float4", "colmax_merge4": "void",
     "ld4s": "float4", "st4s": "void", "lrelu": "float", "dlrelu": "float", "drop_scale": "float",
+    "clamp_idx": "int64_t",
 }
 # the one overload that stays local: ld4 of a global-address-space pointer (ppgat_gemm.hip)
 LOCAL_OVERLOADS = {("ppgat_gemm.hip", "ld4"): r"\(\s*gfloat\s*\*"}
