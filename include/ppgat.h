@@ -765,6 +765,63 @@ int ppgat_neighbor_derive(const int32_t* colptr, const int32_t* row, const int32
                           int32_t* csc_eid_s, int32_t* csc2csr_s, int32_t* csr2csc_s, void* workspace,
                           size_t workspace_bytes, void* stream);
 
+/* ---- seed-subgraph sampling: the L-hop sampled in-neighbourhood of a seed set ---------------
+ * Replaces: nothing in the reference, which trains on the whole graph at every step.  What PyG
+ *   calls NeighborLoader: a mini-batch names its seed nodes, only their sampled neighbourhood is
+ *   extracted and relabelled into a small graph, and the step's work scales with the batch.
+ * The rule.  Inputs: the parent graph over n_nodes nodes, the cap rule above (fanout, fanout_of), a
+ *   64-bit seed, seed nodes T (int64, any order, duplicates allowed), hops = L in [0, 8].  Let S be
+ *   the edge set the fan-out sampler keeps under (fanout, fanout_of, seed): a row's sample depends
+ *   on (seed, i, d, f) alone, i the node's GLOBAL id, so the subgraph is a restriction of S.
+ *     depth(v) = 0 for v in T; else 1 + the least depth of a destination v feeds through an edge
+ *                of S; unreached nodes have none.
+ *     V = {depth <= L};  X = {depth < L}, the expanded nodes.
+ *     K = {e in S : dst(e) in X}, so every source of K is in V.
+ *     n_id = V ascending (users precede items); a node's local id is its position in n_id; the
+ *     kept edges stay in ascending original edge id.
+ *   L = 0 gives the unique seeds and no edges; an empty T gives an empty subgraph.
+ * Outputs: n_id [N_s] int64, depth [N_s] int32, n_users_s = #{n_id < n_users}, edge_index_s
+ *   [2, E_s] int64 in local ids, eid [E_s] int64 (the original columns), seed_local [n_seeds] int64
+ *   in the order of T, and the CSR / CSC views over N_s nodes, every array equal, element for
+ *   element, to ppgat_csr_build of edge_index_s.  Relabelling is monotone, so the views are
+ *   compactions of the parent's (no sort): the edge side is ppgat_neighbor_count / _sample /
+ *   _derive under a cap table that is 0 outside X, the node side a scan of the reached flags.
+ * The calls, on one stream, share one workspace (ppgat_subgraph_workspace_bytes(n_nodes),
+ * host-only) which the caller leaves untouched between them:
+ * ppgat_subgraph_seed: clears info [4] int32 and the depths, gives every seed depth 0; a seed
+ *   outside [0, n_nodes) sets info[2] = 1 (and is otherwise ignored).
+ * ppgat_subgraph_expand, once per hop = 0 .. L - 1 in order: the rows of depth hop give depth
+ *   hop + 1 to the sources of their kept slots that have none (rowptr, col: the parent's CSR).
+ * ppgat_subgraph_plan: cap [n_nodes] int32 = the cap of the rows in X (fanout, or the row's
+ *   fanout_of entry as it stands), 0 elsewhere -- the fanout_of of the ppgat_neighbor_count call
+ *   that follows; info[0] = N_s, info[1] = n_users_s; info[3] = 1 if any fanout_of entry exceeds
+ *   the maximum.  The caller reads info together with ppgat_neighbor_count's: the one host sync.
+ * ppgat_subgraph_relabel, after ppgat_neighbor_sample / _derive wrote rowptr_p, colptr_p
+ *   [n_nodes + 1], col_s, row_s [n_kept] and edge_index_s [2, n_kept] in parent ids: writes n_id,
+ *   depth [n_sub], rowptr_s, colptr_s [n_sub + 1], seed_local [n_seeds], and relabels col_s, row_s
+ *   and edge_index_s in place.  n_sub = N_s and n_kept = E_s as read from the info arrays.
+ * Refused before any device work: fanout outside [1, max] -> PPGAT_ERR_UNSUPPORTED; hop outside
+ *   [0, 8), hops outside [0, 8], a negative size, n_users or n_sub above n_nodes, a NULL required
+ *   pointer (the per-node, per-edge and per-seed ones only when that count is > 0; fanout_of may
+ *   be NULL) or a short workspace -> PPGAT_ERR_INVALID; sizes >= 2^31 -> PPGAT_ERR_UNSUPPORTED.
+ *   Integers only, no atomics: a depth or a flag may be stored by several threads, always with
+ *   the same value, so two calls give the same bits.  Nothing past an output's stated length is
+ *   written. */
+int ppgat_subgraph_max_hops(void);
+int ppgat_subgraph_workspace_bytes(int64_t n_nodes, size_t* bytes);
+int ppgat_subgraph_seed(const int64_t* seeds, int64_t n_seeds, int64_t n_nodes, int32_t* info, void* workspace,
+                        size_t workspace_bytes, void* stream);
+int ppgat_subgraph_expand(const int32_t* rowptr, const int32_t* col, int64_t n_nodes, int64_t n_edges, int hop,
+                          int fanout, const int32_t* fanout_of, uint64_t seed, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int ppgat_subgraph_plan(int64_t n_nodes, int64_t n_users, int hops, int fanout, const int32_t* fanout_of,
+                        int32_t* cap, int32_t* info, void* workspace, size_t workspace_bytes, void* stream);
+int ppgat_subgraph_relabel(int64_t n_nodes, int64_t n_sub, int64_t n_kept, const int64_t* seeds, int64_t n_seeds,
+                           const int32_t* rowptr_p, const int32_t* colptr_p, int64_t* n_id, int32_t* depth,
+                           int32_t* rowptr_s, int32_t* colptr_s, int32_t* col_s, int32_t* row_s,
+                           int64_t* edge_index_s, int64_t* seed_local, void* workspace, size_t workspace_bytes,
+                           void* stream);
+
 /* ---- sampled ranking (evaluation) ------------------------------------------------
  * Replaces: the per-user loop of eval_sampled, scripts/train_gat_pyg.py:160-175:
  *   scores = I[cands[b]] @ U[users[b]];  rank[b] = #(scores[1:] > scores[0]) + 1

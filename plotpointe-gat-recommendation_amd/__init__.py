@@ -13,11 +13,13 @@ from .conv import GATConv, GATv2Conv, SimpleGATLayer  # noqa: F401
 from .evaluation import eval_full, eval_topk, full_rank, recommend_topk, topk_metrics  # noqa: F401
 from .hip_ops import CSRGraph, csr_build, gat_aggregate, gatv2_aggregate, graph_cache  # noqa: F401
 from .lightgcn import LightGCN  # noqa: F401
-from .neighbors import NeighborSampler, sample_neighbors  # noqa: F401
-from .model import CustomGAT, PyGGAT, PyGGATv2, bpr_loss, shared_softmax_loss, softmax_loss  # noqa: F401
+from .neighbors import NeighborSampler, Subgraph, SubgraphSampler, sample_neighbors, sample_subgraph  # noqa: F401
+from .model import (CustomGAT, PyGGAT, PyGGATv2, bpr_loss, forward_subgraph, shared_softmax_loss,  # noqa: F401
+                    softmax_loss)
 
 _sys.modules.setdefault("ppgat_amd", _sys.modules[__name__])
 
 __all__ = ["GATConv", "GATv2Conv", "SimpleGATLayer", "PyGGAT", "PyGGATv2", "CustomGAT", "LightGCN", "lightgcn", "bpr_loss", "softmax_loss", "shared_softmax_loss", "CSRGraph", "csr_build",
            "gat_aggregate", "gatv2_aggregate", "graph_cache", "data", "eval_full", "full_rank", "recommend_topk",
-           "topk_metrics", "eval_topk", "NeighborSampler", "sample_neighbors"]
+           "topk_metrics", "eval_topk", "NeighborSampler", "sample_neighbors", "Subgraph", "SubgraphSampler",
+           "sample_subgraph", "forward_subgraph"]

@@ -223,6 +223,43 @@ def neighbor_derive(g, n_kept: int, colptr_s, row_s, csc_eid_s, csc2csr_s, csr2c
                                        ptr(ws), nbytes, stream_handle(colptr_s.device)), "neighbor_derive")
 
 
+# seed-subgraph sampling (ppgat_subgraph_*); ``g``: the parent hip_ops.CSRGraph.  seed, expand per
+# hop, plan, then neighbor_count / _sample / _derive under the plan's cap table, then relabel: one
+# stream, ``ws`` (subgraph_workspace) untouched in between.  ``info`` [4] int32.
+def subgraph_workspace(n_nodes: int, dev):
+    return workspace(load().ppgat_subgraph_workspace_bytes, n_nodes, device=dev, floor=1)
+
+
+def subgraph_seed(seeds, n_nodes: int, info, ws, nbytes: int):
+    T = seeds.numel()
+    check(load().ppgat_subgraph_seed(ptr(seeds) if T else None, T, n_nodes, ptr(info), ptr(ws), nbytes,
+                                     stream_handle(info.device)), "subgraph_seed")
+
+
+def subgraph_expand(g, hop: int, fanout: int, fanout_of, seed, ws, nbytes: int):
+    check(load().ppgat_subgraph_expand(ptr(g.rowptr), *edge_ptrs(g.n_edges, g.col), g.n_nodes, g.n_edges, int(hop),
+                                       int(fanout), ptr(fanout_of), seed64(seed), ptr(ws), nbytes,
+                                       stream_handle(g.rowptr.device)), "subgraph_expand")
+
+
+def subgraph_plan(n_nodes: int, n_users: int, hops: int, fanout: int, fanout_of, cap, info, ws, nbytes: int):
+    """cap [N] int32 (0 outside the expanded nodes) and info[0:2] = (N_s, n_users_s), info[3] = bad fanout_of."""
+    check(load().ppgat_subgraph_plan(n_nodes, int(n_users), int(hops), int(fanout), ptr(fanout_of),
+                                     ptr(cap) if n_nodes else None, ptr(info), ptr(ws), nbytes,
+                                     stream_handle(info.device)), "subgraph_plan")
+
+
+def subgraph_relabel(n_nodes: int, n_sub: int, n_kept: int, seeds, rowptr_p, colptr_p, n_id, depth, rowptr_s,
+                     colptr_s, col_s, row_s, edge_index_s, seed_local, ws, nbytes: int):
+    """The node side compacted, the edge side relabelled in place (col_s, row_s, edge_index_s)."""
+    T = seeds.numel()
+    check(load().ppgat_subgraph_relabel(n_nodes, n_sub, n_kept, ptr(seeds) if T else None, T, ptr(rowptr_p),
+                                        ptr(colptr_p), *edge_ptrs(n_sub, n_id, depth), ptr(rowptr_s), ptr(colptr_s),
+                                        *edge_ptrs(n_kept, col_s, row_s, edge_index_s),
+                                        ptr(seed_local) if T else None, ptr(ws), nbytes,
+                                        stream_handle(rowptr_s.device)), "subgraph_relabel")
+
+
 # the aggregate-then-transform layer (ppgat_xgat_*); ``v``: a hip_ops.XViews
 def xgat_weights(W, a_s, a_d, H: int, C: int, A=None, Wt=None, Wg=None):
     """Whichever of A [2, H, K] (needs a_s, a_d), Wt [H * K, C] and Wg [C, H * K] are given."""

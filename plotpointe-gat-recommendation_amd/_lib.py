@@ -155,6 +155,13 @@ SIGNATURES = {
                                       c_vp, c_vp, c_sz, c_vp]),
     "ppgat_neighbor_derive": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
                                       c_vp, c_sz, c_vp]),
+    "ppgat_subgraph_max_hops": (c_int, []),
+    "ppgat_subgraph_workspace_bytes": (c_int, [c_i64, ctypes.POINTER(c_sz)]),
+    "ppgat_subgraph_seed": (c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_sz, c_vp]),
+    "ppgat_subgraph_expand": (c_int, [c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_u64, c_vp, c_sz, c_vp]),
+    "ppgat_subgraph_plan": (c_int, [c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "ppgat_subgraph_relabel": (c_int, [c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                       c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "ppgat_sampled_rank": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "ppgat_full_rank_supported": (c_int, [c_int]),
     "ppgat_full_rank_workspace_bytes": (c_int, [c_i64, c_i64, c_int, ctypes.POINTER(c_sz)]),

@@ -1491,6 +1491,100 @@ int ppgat_neighbor_derive(const int32_t* colptr, const int32_t* row, const int32
   return PPGAT_OK;
 }
 
+int ppgat_subgraph_max_hops(void) { return ppgat::kMaxHops; }
+
+static int subgraph_common(int64_t n_nodes, const void* workspace, size_t workspace_bytes, const char* who) {
+  if (n_nodes < 0) return fail(PPGAT_ERR_INVALID, std::string(who) + ": bad sizes (n_nodes >= 0)");
+  if (n_nodes >= ((int64_t)1 << 31) - 1) return fail(PPGAT_ERR_UNSUPPORTED, std::string(who) + ": nodes must be < 2^31 - 1");
+  if (!workspace || workspace_bytes < ppgat::subgraph_workspace_bytes(n_nodes))
+    return fail(PPGAT_ERR_INVALID, std::string(who) + ": workspace too small");
+  return 0;
+}
+
+int ppgat_subgraph_workspace_bytes(int64_t n_nodes, size_t* bytes) {
+  if (!bytes) return fail(PPGAT_ERR_INVALID, "subgraph_workspace_bytes: null pointer");
+  if (n_nodes < 0) return fail(PPGAT_ERR_INVALID, "subgraph_workspace_bytes: bad sizes (n_nodes >= 0)");
+  if (n_nodes >= ((int64_t)1 << 31) - 1)
+    return fail(PPGAT_ERR_UNSUPPORTED, "subgraph_workspace_bytes: nodes must be < 2^31 - 1");
+  *bytes = ppgat::subgraph_workspace_bytes(n_nodes);
+  return PPGAT_OK;
+}
+
+int ppgat_subgraph_seed(const int64_t* seeds, int64_t n_seeds, int64_t n_nodes, int32_t* info, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+  if (n_seeds < 0) return fail(PPGAT_ERR_INVALID, "subgraph_seed: bad sizes (n_seeds >= 0)");
+  if (n_seeds >= (int64_t)1 << 31) return fail(PPGAT_ERR_UNSUPPORTED, "subgraph_seed: seeds must be < 2^31");
+  if (!info || (n_seeds > 0 && !seeds)) return fail(PPGAT_ERR_INVALID, "subgraph_seed: null pointer");
+  if (int rc = subgraph_common(n_nodes, workspace, workspace_bytes, "subgraph_seed")) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  Timed t(PPGAT_K_SAMPLE, st);
+  hipError_t e = ppgat::subgraph_seed(seeds, n_seeds, n_nodes, info, workspace, workspace_bytes, st);
+  if (e != hipSuccess) return hip_fail(e, "subgraph_seed");
+  return PPGAT_OK;
+}
+
+int ppgat_subgraph_expand(const int32_t* rowptr, const int32_t* col, int64_t n_nodes, int64_t n_edges, int hop,
+                          int fanout, const int32_t* fanout_of, uint64_t seed, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+  if (fanout < 1 || fanout > ppgat::kMaxFanout)
+    return fail(PPGAT_ERR_UNSUPPORTED, "subgraph_expand: fanout must be in [1, 64] (one lane per kept neighbour)");
+  if (hop < 0 || hop >= ppgat::kMaxHops) return fail(PPGAT_ERR_INVALID, "subgraph_expand: hop must be in [0, 8)");
+  if (int rc = neighbor_sizes(n_nodes, n_edges, 0, "subgraph_expand")) return rc;
+  if (!rowptr || (n_edges > 0 && !col)) return fail(PPGAT_ERR_INVALID, "subgraph_expand: null pointer");
+  if (int rc = subgraph_common(n_nodes, workspace, workspace_bytes, "subgraph_expand")) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = debug_range(rowptr, 4, n_nodes + 1, 0, n_edges + 1, "subgraph_expand: rowptr", st)) return rc;
+  if (int rc = debug_range(col, 4, n_edges, 0, n_nodes, "subgraph_expand: col", st)) return rc;
+  Timed t(PPGAT_K_SAMPLE, st);
+  hipError_t e = ppgat::subgraph_expand(rowptr, col, n_nodes, hop, fanout, fanout_of, seed, workspace,
+                                        workspace_bytes, st);
+  if (e != hipSuccess) return hip_fail(e, "subgraph_expand");
+  return PPGAT_OK;
+}
+
+int ppgat_subgraph_plan(int64_t n_nodes, int64_t n_users, int hops, int fanout, const int32_t* fanout_of,
+                        int32_t* cap, int32_t* info, void* workspace, size_t workspace_bytes, void* stream) {
+  if (fanout < 1 || fanout > ppgat::kMaxFanout)
+    return fail(PPGAT_ERR_UNSUPPORTED, "subgraph_plan: fanout must be in [1, 64] (one lane per kept neighbour)");
+  if (hops < 0 || hops > ppgat::kMaxHops) return fail(PPGAT_ERR_INVALID, "subgraph_plan: hops must be in [0, 8]");
+  if (n_users < 0 || n_users > n_nodes)
+    return fail(PPGAT_ERR_INVALID, "subgraph_plan: bad sizes (0 <= n_users <= n_nodes)");
+  if (!info || (n_nodes > 0 && !cap)) return fail(PPGAT_ERR_INVALID, "subgraph_plan: null pointer");
+  if (int rc = subgraph_common(n_nodes, workspace, workspace_bytes, "subgraph_plan")) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  Timed t(PPGAT_K_SAMPLE, st);
+  hipError_t e = ppgat::subgraph_plan(n_nodes, n_users, hops, fanout, fanout_of, cap, info, workspace,
+                                      workspace_bytes, st);
+  if (e != hipSuccess) return hip_fail(e, "subgraph_plan");
+  return PPGAT_OK;
+}
+
+int ppgat_subgraph_relabel(int64_t n_nodes, int64_t n_sub, int64_t n_kept, const int64_t* seeds, int64_t n_seeds,
+                           const int32_t* rowptr_p, const int32_t* colptr_p, int64_t* n_id, int32_t* depth,
+                           int32_t* rowptr_s, int32_t* colptr_s, int32_t* col_s, int32_t* row_s,
+                           int64_t* edge_index_s, int64_t* seed_local, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+  if (n_sub < 0 || n_sub > n_nodes || n_kept < 0 || n_seeds < 0)
+    return fail(PPGAT_ERR_INVALID, "subgraph_relabel: bad sizes (0 <= n_sub <= n_nodes, n_kept >= 0, n_seeds >= 0)");
+  if (n_kept >= (int64_t)1 << 31 || n_seeds >= (int64_t)1 << 31)
+    return fail(PPGAT_ERR_UNSUPPORTED, "subgraph_relabel: edges and seeds must be < 2^31");
+  if (!rowptr_p || !colptr_p || !rowptr_s || !colptr_s || (n_sub > 0 && (!n_id || !depth)) ||
+      (n_kept > 0 && (!col_s || !row_s || !edge_index_s)) || (n_seeds > 0 && (!seeds || !seed_local)))
+    return fail(PPGAT_ERR_INVALID, "subgraph_relabel: null pointer");
+  if (int rc = subgraph_common(n_nodes, workspace, workspace_bytes, "subgraph_relabel")) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = debug_range(rowptr_p, 4, n_nodes + 1, 0, n_kept + 1, "subgraph_relabel: rowptr_p", st)) return rc;
+  if (int rc = debug_range(colptr_p, 4, n_nodes + 1, 0, n_kept + 1, "subgraph_relabel: colptr_p", st)) return rc;
+  if (int rc = debug_range(col_s, 4, n_kept, 0, n_nodes, "subgraph_relabel: col_s", st)) return rc;
+  if (int rc = debug_range(row_s, 4, n_kept, 0, n_nodes, "subgraph_relabel: row_s", st)) return rc;
+  Timed t(PPGAT_K_SAMPLE, st);
+  hipError_t e = ppgat::subgraph_relabel(n_nodes, n_sub, n_kept, seeds, n_seeds, rowptr_p, colptr_p, n_id, depth,
+                                         rowptr_s, colptr_s, col_s, row_s, edge_index_s, seed_local, workspace,
+                                         workspace_bytes, st);
+  if (e != hipSuccess) return hip_fail(e, "subgraph_relabel");
+  return PPGAT_OK;
+}
+
 int ppgat_eval_sample(const int64_t* user_ptr, const int32_t* items_sorted, const int64_t* users, const int64_t* pos,
                       int64_t n_eval, int64_t n_neg, int64_t n_items, uint64_t seed, int64_t* cands, int32_t* bad,
                       void* stream) {

@@ -235,6 +235,24 @@ hipError_t neighbor_derive(const int32_t* colptr, const int32_t* row, const int3
                            int64_t N, int64_t E, int64_t Es, int32_t* colptr_s, int32_t* row_s, int32_t* csc_eid_s,
                            int32_t* csc2csr_s, int32_t* csr2csc_s, void* ws, size_t ws_bytes, hipStream_t st);
 
+// seed-subgraph sampling (ppgat_subgraph.hip): the L-hop sampled in-neighbourhood of a seed set.
+// seed -> expand (hop 0 .. L - 1) -> plan -> neighbor_count with the plan's cap table -> (host reads
+// the two info arrays) -> neighbor_sample -> neighbor_derive -> relabel; one workspace
+// (subgraph_workspace_bytes) carried through its own four, untouched in between.
+// info [4] = (N_s, n_users_s, bad seed, bad fanout_of entry)
+constexpr int kMaxHops = 8;
+size_t subgraph_workspace_bytes(int64_t N);
+hipError_t subgraph_seed(const int64_t* seeds, int64_t T, int64_t N, int32_t* info, void* ws, size_t ws_bytes,
+                         hipStream_t st);
+hipError_t subgraph_expand(const int32_t* rowptr, const int32_t* col, int64_t N, int hop, int fanout,
+                           const int32_t* fanout_of, uint64_t seed, void* ws, size_t ws_bytes, hipStream_t st);
+hipError_t subgraph_plan(int64_t N, int64_t n_users, int hops, int fanout, const int32_t* fanout_of, int32_t* cap,
+                         int32_t* info, void* ws, size_t ws_bytes, hipStream_t st);
+hipError_t subgraph_relabel(int64_t N, int64_t Ns, int64_t Es, const int64_t* seeds, int64_t T,
+                            const int32_t* rowptr_p, const int32_t* colptr_p, int64_t* n_id, int32_t* depth_s,
+                            int32_t* rowptr_s, int32_t* colptr_s, int32_t* col_s, int32_t* row_s, int64_t* ei_s,
+                            int64_t* seed_local, void* ws, size_t ws_bytes, hipStream_t st);
+
 // evaluation (ppgat_eval.hip)
 hipError_t serve_topk(const float* iv, int64_t n_items, int C, const int64_t* hptr, const int64_t* hist,
                       int64_t max_hist, int B, int k, float* U, float* scores, int32_t* out_idx, float* out_score,

@@ -17,6 +17,7 @@
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
+#include "ppgat_floyd.h"
 #include "ppgat_internal.h"
 
 namespace ppgat {
@@ -25,17 +26,6 @@ namespace {
 constexpr int kRows = 256;  // destination rows per block of the pick
 
 inline size_t align_up(size_t b) { return (b + 255) & ~size_t(255); }
-
-// the counter stream of ppgat_sample.hip (draw64 / below), restated: oracle/sampler_oracle.py
-__device__ __forceinline__ uint64_t draw64(uint64_t seed, uint64_t t, uint64_t k) {
-  uint64_t z = seed + (t + 1) * 0x9E3779B97F4A7C15ull;
-  z ^= (k + 1) * 0xD1B54A32D192ED03ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ int64_t below(uint64_t r, int64_t n) { return (int64_t)__umul64hi(r, (uint64_t)n); }
 
 struct ByteFlag {
   __host__ __device__ int32_t operator()(uint8_t v) const { return (int32_t)v; }
@@ -167,14 +157,7 @@ __global__ void __launch_bounds__(256) k_pick(const int32_t* __restrict__ rowptr
     const int32_t d = __builtin_amdgcn_readfirstlane(s_rp[r + 1] - s_rp[r]);
     const int32_t f = __builtin_amdgcn_readfirstlane(s_rps[r + 1] - s_rps[r]);
     const uint64_t i = (uint64_t)(r0 + r);
-    const int32_t tl =
-        lane < f ? (int32_t)below(draw64(seed, i, (uint64_t)lane), (int64_t)(d - f + lane) + 1) : -1;
-    int32_t val = -1;  // lane s: element s of S once step s has run
-    for (int s = 0; s < f; ++s) {
-      const int32_t t = __builtin_amdgcn_readlane(tl, s);
-      const bool hit = __ballot(val == t) != 0;  // lanes >= s still hold -1 and t >= 0
-      if (lane == s) val = hit ? d - f + s : t;
-    }
+    const int32_t val = floyd_wave(seed, i, d, f, lane);  // lane s: element s of S
     int rank = 0;
     for (int l = 0; l < f; ++l) rank += __builtin_amdgcn_readlane(val, l) < val ? 1 : 0;
     if (lane < f) {

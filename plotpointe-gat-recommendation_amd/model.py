@@ -91,6 +91,30 @@ def _stack(model, item_proj, item_feats, layers, edge_index, edge_attr=None):
     return x
 
 
+def forward_subgraph(model, item_feats, sub, edge_attr=None):
+    """The layer stack on a ``neighbors.Subgraph``: ``Z_s [N_s, d]``, row k the embedding of node
+    ``sub.n_id[k]`` (exact at the seeds when ``hops`` = the number of layers: a seed's output reads
+    its sampled neighbourhood to that depth and no further).  Only the subgraph's nodes are touched:
+    user rows are ``user_emb.weight.index_select(0, n_id[:n_users_s])``, item rows the projection of
+    the subgraph's items alone -- the node-side saving -- and the node table of ``_stack`` is not
+    used.  The embedding gradient arrives through ``index_select``'s backward; ``n_id`` is unique,
+    so each row is added once.  ``edge_attr``: the PARENT graph's [E, D] tensor, gathered by
+    ``sub.eid`` here."""
+    layers = model.convs if hasattr(model, "convs") else model.layers
+    nu = sub.n_users_s
+    xu = model.user_emb.weight.index_select(0, sub.n_id[:nu])
+    if sub.n_nodes > nu:
+        feats = item_feats.index_select(0, sub.n_id[nu:] - model.n_users)
+        xv = hip_ops.linear(feats, model.item_proj.weight, model.item_proj.bias)
+    else:
+        xv = xu.new_zeros((0, xu.size(1)))
+    x = torch.cat([xu, xv], dim=0)
+    ea = {} if edge_attr is None else {"edge_attr": edge_attr.index_select(0, sub.eid)}
+    for layer in layers:
+        x = layer(x, sub.edge_index_s, **ea)
+    return x
+
+
 def layer_attention(model, layers, item_feats, edge_index, edge_attr=None, order: str = "edge", only=None):
     """The attention weights of a model's layer stack: a list with one [E, H] fp32 tensor per layer
     (``only``: that layer alone, the stack run no further), alpha before the dropout mask, row k
@@ -144,6 +168,10 @@ class PyGGAT(torch.nn.Module):
     def forward(self, item_feats: torch.Tensor, edge_index: torch.Tensor, edge_attr=None) -> torch.Tensor:
         return _stack(self, self.item_proj, item_feats, self.convs, edge_index, edge_attr)
 
+    def forward_subgraph(self, item_feats: torch.Tensor, sub, edge_attr=None) -> torch.Tensor:
+        """``Z_s [N_s, hidden]`` on a ``neighbors.Subgraph`` (model.forward_subgraph)."""
+        return forward_subgraph(self, item_feats, sub, edge_attr)
+
     def attention(self, item_feats: torch.Tensor, edge_index: torch.Tensor, edge_attr=None, order: str = "edge"):
         """One [E, H] attention tensor per layer (layer_attention)."""
         return layer_attention(self, self.convs, item_feats, edge_index, edge_attr, order)
@@ -174,6 +202,12 @@ class PyGGATv2(torch.nn.Module):
     def forward(self, item_feats: torch.Tensor, edge_index: torch.Tensor) -> torch.Tensor:
         return _stack(self, self.item_proj, item_feats, self.convs, edge_index)
 
+    def forward_subgraph(self, item_feats: torch.Tensor, sub, edge_attr=None) -> torch.Tensor:
+        """``Z_s [N_s, hidden]`` on a ``neighbors.Subgraph`` (model.forward_subgraph); no ``edge_attr``."""
+        if edge_attr is not None:
+            raise NotImplementedError("PyGGATv2: edge features are not implemented")
+        return forward_subgraph(self, item_feats, sub)
+
     def attention(self, item_feats: torch.Tensor, edge_index: torch.Tensor, edge_attr=None, order: str = "edge"):
         """One [E, H] attention tensor per layer (layer_attention); GATv2Conv takes no ``edge_attr``."""
         if edge_attr is not None:
@@ -198,6 +232,12 @@ class CustomGAT(torch.nn.Module):
 
     def forward(self, item_feats: torch.Tensor, edge_index: torch.Tensor) -> torch.Tensor:
         return _stack(self, self.item_proj, item_feats, self.layers, edge_index)
+
+    def forward_subgraph(self, item_feats: torch.Tensor, sub, edge_attr=None) -> torch.Tensor:
+        """``Z_s [N_s, hidden]`` on a ``neighbors.Subgraph`` (model.forward_subgraph); no ``edge_attr``."""
+        if edge_attr is not None:
+            raise NotImplementedError("CustomGAT: edge features are not implemented")
+        return forward_subgraph(self, item_feats, sub)
 
     def attention(self, item_feats: torch.Tensor, edge_index: torch.Tensor, edge_attr=None, order: str = "edge"):
         """One [E, 1] attention tensor per layer (layer_attention); the custom layer takes no ``edge_attr``."""

@@ -235,6 +235,68 @@ def check_fanout(args):
         raise ValueError("--resample-every must be >= 1")
 
 
+def check_subgraph_batch(args):
+    """--subgraph-batch B > 0 (mini-batch training on seed subgraphs, neighbors.SubgraphSampler): the
+    GAT families on one GPU, private negatives only; it restricts the --fanout sampled graph, so it
+    needs --fanout >= 1, and every batch draws its own sample (--resample-every 1)."""
+    if args.subgraph_batch == 0:
+        return
+    if args.subgraph_batch < 0:
+        raise ValueError(f"--subgraph-batch {args.subgraph_batch}: expected >= 0 (0 = off)")
+    if args.model_family == "lightgcn":
+        raise NotImplementedError("--subgraph-batch with --model-family lightgcn is not implemented: the LightGCN "
+                                  "trainer has its own mini-batch loop over the whole normalised adjacency")
+    if args.world_size > 1:
+        raise NotImplementedError(f"--subgraph-batch with --world-size {args.world_size} is not implemented: the "
+                                  "sharded trainers partition the whole graph once (--world-size 1)")
+    if args.shared_negatives > 0:
+        raise NotImplementedError(f"--subgraph-batch with --shared-negatives {args.shared_negatives} is not "
+                                  "implemented: the shared pool and the history mask are keyed by global item ids")
+    if args.fanout < 1:
+        raise ValueError("--subgraph-batch needs --fanout >= 1: a subgraph is a restriction of the sampled graph")
+    if args.resample_every != 1:
+        raise ValueError("--subgraph-batch draws a sample per batch: --resample-every must stay 1")
+
+
+def subgraph_epoch(model, opt, item_feats, sub_sampler, epoch: int, batch: int, n_users: int, u, i, j,
+                   loss: str = "bpr", edge_attr=None, softmax=None):
+    """One epoch of mini-batch steps on seed subgraphs.  The epoch's triples (or ``softmax`` =
+    (cand [S, M + 1], temperature[, logQ table by global item id])) are cut in order into
+    ceil(S / batch) batches; per batch the seeds are its users and ``n_users +`` its items, the
+    subgraph is ``sub_sampler.batch(epoch - 1, b, seeds)``, and forward, loss (on ``seed_local``:
+    the seeds' local ids in the seeds' order), zero_grad, backward and ``opt.step()`` run on it.
+    Returns (the sample-weighted mean loss, a 0-d tensor; batches; mean nodes; mean edges)."""
+    S = int(u.numel())
+    n_batches = (S + batch - 1) // batch
+    total = torch.zeros((), dtype=torch.float32, device=u.device)
+    nodes = edges = 0
+    for b in range(n_batches):
+        lo_, hi_ = b * batch, min(S, (b + 1) * batch)
+        s = hi_ - lo_
+        if softmax is not None:
+            cand, temperature, *corr = softmax
+            items = cand[lo_:hi_].reshape(-1)
+        else:
+            items = torch.cat([i[lo_:hi_], j[lo_:hi_]])
+        sub = sub_sampler.batch(epoch - 1, b, torch.cat([u[lo_:hi_], items + n_users]))
+        nus = sub.n_users_s
+        ul, il = sub.seed_local[:s].contiguous(), sub.seed_local[s:] - nus
+        Z = model.forward_subgraph(item_feats, sub, edge_attr)
+        if softmax is not None:
+            corr_s = corr[0].index_select(0, sub.n_id[nus:] - n_users) if corr else None
+            lo = model_mod.softmax_loss(Z, nus, ul, il.view(s, -1), temperature, correction=corr_s)
+        else:
+            lo = model_mod.bpr_loss(Z, nus, ul, il[:s].contiguous(), il[s:].contiguous(), loss)
+        opt.zero_grad()
+        lo.backward()
+        opt.step()
+        total += lo.detach() * s
+        nodes += sub.n_nodes
+        edges += sub.n_edges
+    d = max(n_batches, 1)
+    return total / max(S, 1), n_batches, nodes / d, edges / d
+
+
 def check_negative_sampling(args) -> bool:
     """--negative-sampling / --popularity-power / --logq -> whether the logQ correction is on.
     Popularity sampling and the correction are the GAT families' on one GPU (refused like --loss
@@ -600,6 +662,10 @@ def build_parser():
                     help="--fanout: the cap of the item destinations instead of F (0..64)")
     ap.add_argument("--resample-every", type=int, default=1, metavar="K",
                     help="--fanout: draw a new sampled graph every K epochs")
+    ap.add_argument("--subgraph-batch", type=int, default=0, metavar="B",
+                    help="--fanout: cut the epoch's triples into batches of B and take one optimiser step per batch, "
+                         "on the --layers-hop sampled subgraph of the batch's users and items alone (0 = off: one "
+                         "step per epoch).  Evaluation and the exports keep the whole graph.  GAT families, one GPU")
     return ap
 
 
@@ -607,6 +673,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     check_edge_features(args)
     check_softmax_loss(args)
+    check_subgraph_batch(args)
     check_fanout(args)
     logq = check_negative_sampling(args)
     if args.recommend_out and args.world_size > 1:
@@ -708,14 +775,18 @@ def main(argv=None):
             weights = sampler_mod.BPRSampler.popularity_weights(ptr, flat, n_items, cfg.popularity_power)
         dev_sampler = sampler_mod.BPRSampler(ptr, flat, n_items, device=device, item_weights=weights)
     ssm_corr = dev_sampler.correction(cfg.negatives) if logq and args.shared_negatives == 0 else None
-    nb_sampler = None
+    nb_sampler = sub_sampler = None
     if args.fanout > 0:  # one GPU (refused above otherwise)
         fanout_of = None
         if args.fanout_items is not None:  # users keep --fanout (-1 would keep all), items take F2
             fanout_of = torch.full((n_users + n_items,), args.fanout, dtype=torch.int32, device=device)
             fanout_of[n_users:] = args.fanout_items
-        nb_sampler = neighbors_mod.NeighborSampler(edge_index, n_users + n_items, args.fanout, seed=cfg.seed,
-                                                   fanout_of=fanout_of)
+        if args.subgraph_batch > 0:  # a sample per batch, restricted to the batch's neighbourhood
+            sub_sampler = neighbors_mod.SubgraphSampler(edge_index, n_users + n_items, cfg.layers, args.fanout,
+                                                        seed=cfg.seed, fanout_of=fanout_of, n_users=n_users)
+        else:
+            nb_sampler = neighbors_mod.NeighborSampler(edge_index, n_users + n_items, args.fanout, seed=cfg.seed,
+                                                       fanout_of=fanout_of)
     step_edges, step_attr = edge_index, edge_attr
     for epoch in range(1, cfg.epochs + 1):
         model.train()
@@ -741,8 +812,13 @@ def main(argv=None):
                 softmax = (dev_sampler.train_candidates(u, i, cfg.negatives, seed=cfg.seed + epoch), cfg.temperature)
                 if logq:
                     softmax += (ssm_corr,)
-            loss_val = float(epoch_step(model, opt, item_feats, step_edges, n_users, u, i, j, cfg.loss,
-                                        edge_attr=step_attr, softmax=softmax, shared=shared).item())
+            if sub_sampler is not None:
+                lo, *sub_stats = subgraph_epoch(model, opt, item_feats, sub_sampler, epoch, args.subgraph_batch,
+                                                n_users, u, i, j, cfg.loss, edge_attr=edge_attr, softmax=softmax)
+                loss_val = float(lo.item())
+            else:
+                loss_val = float(epoch_step(model, opt, item_feats, step_edges, n_users, u, i, j, cfg.loss,
+                                            edge_attr=step_attr, softmax=softmax, shared=shared).item())
         else:
             # each rank: its own users' triples (the sum over ranks is the reference's mean),
             # dense gradients all-reduced, user rows updated by their owner
@@ -766,6 +842,8 @@ def main(argv=None):
             print(f"[{tag}][Epoch {epoch}] val: {val_metrics}")
         if args.structured_logs and lead:
             sampled = {"sampled_edges": int(step_edges.size(1))} if nb_sampler is not None else {}
+            if sub_sampler is not None:
+                sampled = {"batches": sub_stats[0], "mean_sub_nodes": sub_stats[1], "mean_sub_edges": sub_stats[2]}
             log_event("epoch_end", run_id=run_id, epoch=epoch, loss=loss_val, val=val_metrics, **sampled)
         if val_metrics.get("ndcg@20", 0.0) > best:
             best = val_metrics.get("ndcg@20", 0.0)
@@ -798,6 +876,9 @@ def main(argv=None):
     if cfg.negative_sampling == "popularity":
         out["notes"] += (f"; negatives drawn in proportion to (train count)^{cfg.popularity_power}, logQ correction "
                          f"{'on' if logq else 'off'}")
+    if sub_sampler is not None:
+        out["notes"] += (f"; --subgraph-batch {args.subgraph_batch}: one optimiser step per batch of triples, on the "
+                         f"{cfg.layers}-hop fan-out {args.fanout} subgraph of the batch's users and items")
     if full:
         out["config"] = {**cfg.__dict__, "eval_mode": "full"}
         out["notes"] += "; " + FULL_EVAL_NOTE
