@@ -167,7 +167,28 @@ int ppgat_bwd(const ppgat_schedule* src_sched, const int32_t* rowptr, const int3
  *  ppgat_bwd_dst_sum_csc); csc2csr as dz_slot gives the CSR-order layout of ppgat_bwd_dst_sum.
  *  nstate: [N_dst, H] float4 {s_dst, m, inv_l, D}.  grad_bias (nullable) needs bias_part
  *  [ppgat_bwd_partial_rows(n) * C]; epilogue part: [ppgat_bwd_partial_rows(n) * 2*H*C].
+ *
+ * Zero-row mark.  D with the bit pattern 0x80000000 (-0.0f) means "this destination's grad_out
+ * row is all zeros".  ppgat_bwd_prologue writes it exactly for those rows and +0.0f for any other
+ * D that is zero; so do the fused producers (ppgat_bpr_bwd_producer: the rows no triple names;
+ * ppgat_project_bwd_fused_producer never marks).  A caller that builds nstate itself must not
+ * store -0.0f in D for a row whose grad_out is not all zeros.
+ *
+ * Gather skipping (ppgat_set_gather_skip, default on).  ppgat_fwd / ppgat_edge_fwd do not load
+ * h_j of an edge whose weight exp(e - m) * dropout is exactly 0; ppgat_bwd_edges /
+ * ppgat_edge_bwd_edges (heads = 1, and the per-head kernel taken when heads is not 2, 4 or 8 or
+ * C < 32) do not load grad_out row i of an edge with beta = c1 = 0 (a dropped edge) or whose
+ * destination carries the zero-row mark.  The skipped terms are exact zeros, so every output
+ * equals the unskipped one, with two exceptions:
+ *  - a non-finite value in a row reached only through such edges no longer makes the result NaN
+ *    (0 x NaN is not computed);
+ *  - dz of a dropped edge whose c0 is exactly 0 may be +0 where it was -0 or the reverse.
+ * The multi-head pass (heads 2, 4, 8), the aggregate-then-transform and the GATv2 kernels gather
+ * every row.  Returns the previous value; read by each launch, so a captured graph keeps the
+ * value it was captured with.  The Python package applies PPGAT_GATHER_SKIP=0 once, when it
+ * loads the library (the library itself does not read the environment).
  */
+int ppgat_set_gather_skip(int on);
 int64_t ppgat_bwd_partial_rows(int64_t n_nodes);
 int ppgat_bwd_prologue(const float* grad_out, const float* out, const float* agg, const float* bias,
                        const float* s_dst, const float* m, const float* inv_l, int64_t n_nodes, int heads,

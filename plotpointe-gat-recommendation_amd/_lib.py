@@ -108,6 +108,7 @@ SIGNATURES = {
     "ppgat_adam_step_device": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_double, ctypes.c_double,
                                        ctypes.c_double, c_f, c_f, c_vp]),
     "ppgat_dropout_advance": (c_int, [c_vp]),
+    "ppgat_set_gather_skip": (c_int, [c_int]),
     "ppgat_rep_merge": (c_int, [c_int, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "ppgat_dropout_set_epoch": (c_int, [ctypes.c_uint64, c_vp]),
     "ppgat_rows_gather": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_i64, c_vp]),
@@ -269,6 +270,8 @@ def load(path: Path = None):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    if os.environ.get("PPGAT_GATHER_SKIP", "1") == "0":  # read once, here (ppgat_set_gather_skip)
+        lib.ppgat_set_gather_skip(0)
     _lib = lib
     return lib
 
@@ -378,6 +381,13 @@ def dropout_advance(device=None):
     lib = load()
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
     check(lib.ppgat_dropout_advance(stream_handle(dev)), "dropout_advance")
+
+
+def set_gather_skip(on: bool) -> bool:
+    """Switch the zero-weight / zero-row gather skipping of the edge kernels (include/ppgat.h
+    ppgat_set_gather_skip; PPGAT_GATHER_SKIP=0, read once by load(), starts a process with it off).  Returns the previous
+    value.  Results are equal either way; a captured graph keeps the value it was captured with."""
+    return bool(load().ppgat_set_gather_skip(1 if on else 0))
 
 
 def dropout_set_epoch(epoch: int, device=None):

@@ -1070,6 +1070,8 @@ int ppgat_rows_return_add(float* dst, int64_t ld_dst, const float* ret, int64_t 
   return PPGAT_OK;
 }
 
+int ppgat_set_gather_skip(int on) { return ppgat::set_gather_skip(on); }
+
 int ppgat_dropout_advance(void* stream) {
   hipError_t e = ppgat::dropout_epoch(0, 0, static_cast<hipStream_t>(stream));
   if (e != hipSuccess) return hip_fail(e, "dropout_advance");

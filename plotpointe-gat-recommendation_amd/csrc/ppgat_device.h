@@ -88,6 +88,19 @@ __device__ __forceinline__ float drop_scale(uint64_t seed, uint32_t eid, uint32_
   return u >= p ? inv_keep : 0.f;
 }
 
+// Gather skipping (include/ppgat.h, ppgat_set_gather_skip).  nstate.w = D with the bit pattern of
+// -0.0f marks a destination whose grad_out row is all zeros; every D writer of the GAT path emits
+// that pattern for such rows only and +0 for any other zero (canon_d).  Pass B needs g_i of an
+// edge for beta g_i and c1 <g_i, h_j> alone: with beta = c1 = 0 (a dropped edge) or a marked row
+// both are exact zeros, so the row is not gathered (grow_unneeded).
+constexpr int kZeroRowBits = (int)0x80000000u;
+__device__ __forceinline__ float canon_d(float d, bool zero_row) {
+  return zero_row ? __int_as_float(kZeroRowBits) : (d == 0.f ? 0.f : d);
+}
+__device__ __forceinline__ bool grow_unneeded(float bg, float c1, float d) {
+  return (bg == 0.f && c1 == 0.f) || __float_as_int(d) == kZeroRowBits;
+}
+
 // Work items, as the edge kernels take them.  Rows (destination rows for a forward, source rows
 // for a backward pass by source) are cut into items of at most T edges by ppgat_schedule_build:
 // hub rows (deg > T) become ceil(deg/T) pieces that write partial state to a scratch slab and are

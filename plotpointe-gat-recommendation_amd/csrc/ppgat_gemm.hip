@@ -1491,7 +1491,7 @@ __global__ void __launch_bounds__(64 * kDxwWaves, 1) k_dxw(DxwArg a) {
       float d = s[0];
 #pragma unroll
       for (int q = 1; q < kDxwWaves; ++q) d += s[q * kDxwRows];
-      a.pnstate[row] = make_float4(pf_s, pf_m, pf_l, d * a.pgscale);
+      a.pnstate[row] = make_float4(pf_s, pf_m, pf_l, canon_d(d * a.pgscale, false));  // never the zero-row mark
     }
     pro_pref(row0 + kDxwRows);
   };

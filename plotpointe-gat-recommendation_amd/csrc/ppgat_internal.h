@@ -32,6 +32,10 @@ hipError_t launch_bwd_src(const ppgat_schedule& sch, const int32_t* row, const i
                           int mode, float slope, float gscale, float p, uint64_t seed, const uint64_t* seed_in,
                           float* dh, int64_t ld_dh, float* ds_src, int64_t ld_ds, float* dz, float* partial,
                           hipStream_t st, const float* et = nullptr);
+// gather skipping in launch_fwd / launch_bwd_src (ppgat_set_gather_skip): the current value, and
+// set-and-return-previous
+int gather_skip();
+int set_gather_skip(int on);
 // edge features (ppgat_egat.hip): attribute staging, per-step logit terms, the dv reduction
 hipError_t edge_attr_permute(const float* attr, const int32_t* eid, int64_t E, int D, float* out, hipStream_t st);
 hipError_t edge_terms(const float* attr_csr, const float* attr_csc, const float* v, int64_t E, int D, int H,

@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
+#include <atomic>
 
 #include "ppgat_internal.h"
 #include "ppgat_lanes.h"
@@ -124,7 +125,7 @@ __global__ void __launch_bounds__(256) k_fwd(Items it, const int32_t* __restrict
                                              uint64_t seed, float* __restrict__ out, float* __restrict__ m_out,
                                              float* __restrict__ invl_out, float* __restrict__ agg_out,
                                              float* __restrict__ partial, uint64_t* __restrict__ seed_out,
-                                             const float* __restrict__ et) {
+                                             const float* __restrict__ et, int gskip) {
   if (p > 0.f) seed = epoch_seed(seed);
   if (seed_out != nullptr && blockIdx.x == 0 && threadIdx.x == 0) seed_out[0] = seed;  // the backward's mask seed
   using G = Geo<C>;
@@ -177,7 +178,9 @@ __global__ void __launch_bounds__(256) k_fwd(Items it, const int32_t* __restrict
           const int q = q0 + u * G::EPW + sg;
           const int2 r = rec[wv][q];
           pq[u] = __int_as_float(r.y);
-          v[u] = q < n ? ld4(h + ((int64_t)r.x * heads + hd) * C + sl * 4) : f4(0.f);
+          // a zero weight (dropped edge, underflowed exp) adds exact zeros: skip its row (gskip)
+          const bool need = q < n && (!gskip || pq[u] != 0.f);
+          v[u] = need ? ld4(h + ((int64_t)r.x * heads + hd) * C + sl * 4) : f4(0.f);
         }
 #pragma unroll
         for (int u = 0; u < G::U; ++u) acc = fma4(pq[u], v[u], acc);
@@ -243,7 +246,7 @@ __global__ void __launch_bounds__(256) k_fwd_short(Items it, int64_t first, cons
                                                    float p, float inv_keep, uint64_t seed, float* __restrict__ out,
                                                    float* __restrict__ m_out, float* __restrict__ invl_out,
                                                    float* __restrict__ agg_out, uint64_t* __restrict__ seed_out,
-                                                   HubMerge mg, const float* __restrict__ et) {
+                                                   HubMerge mg, const float* __restrict__ et, int gskip) {
   if (p > 0.f) seed = epoch_seed(seed);
   if (seed_out != nullptr && blockIdx.x == 0 && threadIdx.x == 0) seed_out[0] = seed;  // the backward's mask seed
   constexpr int NV = C / 64;  // float4 columns per lane
@@ -298,8 +301,9 @@ __global__ void __launch_bounds__(256) k_fwd_short(Items it, int64_t first, cons
       const int t = t0 + u;
       const int2 r = rq[t & 15];
       wt[u] = t < n ? __int_as_float(r.y) : 0.f;
+      const bool need = t < n && (!gskip || wt[u] != 0.f);  // zero weight: the row adds exact zeros
 #pragma unroll
-      for (int c = 0; c < NV; ++c) v[u][c] = t < n ? ld4(h + (int64_t)r.x * C + (ql + 16 * c) * 4) : f4(0.f);
+      for (int c = 0; c < NV; ++c) v[u][c] = need ? ld4(h + (int64_t)r.x * C + (ql + 16 * c) * 4) : f4(0.f);
     }
 #pragma unroll
     for (int u = 0; u < kSU; ++u)
@@ -462,7 +466,7 @@ __global__ void __launch_bounds__(256) k_attn_short(Items it, int64_t first, con
 // Backward prologue, one subgroup per (n, h), grid-stride over a fixed grid:
 //   D[n,h] = <g_n, agg[n,h]>, g = gscale * grad_out   (= sum_k alpha_k dalpha_k, Appendix B)
 // and the per-node state pass B gathers once per edge, packed as one float4:
-//   nstate[n,h] = {s_dst, m, inv_l, D}
+//   nstate[n,h] = {s_dst, m, inv_l, D}     (D = -0.0f exactly when g_n is all zeros: canon_d)
 // When bias_part != NULL also the block partial column sums of grad_out (dbias), in a
 // fixed order (subgroups in order within a block, blocks reduced by k_col_reduce).
 // ---------------------------------------------------------------------------
@@ -502,7 +506,11 @@ __global__ void __launch_bounds__(256) k_bwd_pro(const float* __restrict__ grad_
         av = make_float4(av.x - b.x, av.y - b.y, av.z - b.z, av.w - b.w);
       }
       float x = group_reduce<Op::Sum, 1, G::LPR / 2>(dot4(g[u], av));
-      if (valid && sl == 0) nstate[pr] = make_float4(s_dst[pr], m_in[pr], invl_in[pr], x * gscale);
+      // all-zero row: no lane of the subgroup holds a non-zero
+      const bool nz = g[u].x != 0.f || g[u].y != 0.f || g[u].z != 0.f || g[u].w != 0.f;
+      const bool zero_row = group_reduce<Op::Max, 1, G::LPR / 2>(nz ? 1.f : 0.f) == 0.f;
+      if (valid && sl == 0)
+        nstate[pr] = make_float4(s_dst[pr], m_in[pr], invl_in[pr], canon_d(x * gscale, zero_row));
     }
   }
   if (bias_part == nullptr) return;
@@ -534,12 +542,14 @@ __global__ void __launch_bounds__(256) k_bwd_src(Items it, const int32_t* __rest
     const uint64_t* __restrict__ seed_in,
                                                  float* __restrict__ dh, int64_t ld_dh, float* __restrict__ ds_src,
                                                  int64_t ld_ds, float* __restrict__ dz, float* __restrict__ partial,
-                                                 const float* __restrict__ et) {
+                                                 const float* __restrict__ et, int gskip) {
   if (p > 0.f) seed = seed_in != nullptr ? *seed_in : epoch_seed(seed);
   using G = Geo<C>;
   constexpr int GRP = G::LPR / G::U;  // lanes sharing one reduced edge value
   // per wave, per chunk edge: {dst row, beta * gscale} and {c1, c0, CSR slot}, where
-  // dz = c1 <g_i, h_j> - c0  (c1 = alpha e' d gscale, c0 = alpha e' D_i)
+  // dz = c1 <g_i, h_j> - c0  (c1 = alpha e' d gscale, c0 = alpha e' D_i).  dst row -1: no g_i to
+  // load -- past the chunk's last edge, or (gskip) an edge that needs none: beta = c1 = 0, a
+  // dropped edge, or a marked all-zero row (grow_unneeded)
   __shared__ int2 recA[4][64];
   __shared__ float4 recB[4][64];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -561,7 +571,7 @@ __global__ void __launch_bounds__(256) k_bwd_src(Items it, const int32_t* __rest
       const bool valid = k < ce;
       const int i = valid ? row[k] : 0;
       float bg = 0.f, c1 = 0.f, c0 = 0.f;
-      int slot = 0;
+      int slot = 0, gi = valid ? i : -1;
       if (valid) {
         const float4 st = nstate[(int64_t)i * heads + hd];  // {s_dst, m, inv_l, D}
         float z = ss + st.x;
@@ -574,8 +584,9 @@ __global__ void __launch_bounds__(256) k_bwd_src(Items it, const int32_t* __rest
         const float a1 = af * dlogit(z, slope, mode);
         c1 = a1 * dm * gscale;
         c0 = a1 * st.w;
+        if (gskip && grow_unneeded(bg, c1, st.w)) gi = -1;
       }
-      recA[wv][lane] = make_int2(i, __float_as_int(bg));
+      recA[wv][lane] = make_int2(gi, __float_as_int(bg));
       recB[wv][lane] = make_float4(c1, c0, __int_as_float(slot), 0.f);
       wave_sync();
       const int n = min(64, ce - base);
@@ -587,7 +598,7 @@ __global__ void __launch_bounds__(256) k_bwd_src(Items it, const int32_t* __rest
           const int q = q0 + u * G::EPW + sg;
           const int2 r = recA[wv][q];
           bq[u] = __int_as_float(r.y);
-          g[u] = q < n ? ld4(grad_out + (int64_t)r.x * C + sl * 4) : f4(0.f);
+          g[u] = r.x >= 0 ? ld4(grad_out + (int64_t)r.x * C + sl * 4) : f4(0.f);  // (-1 past the chunk's end too)
         }
 #pragma unroll
         for (int u = 0; u < G::U; ++u) {
@@ -639,7 +650,7 @@ __global__ void __launch_bounds__(256) k_bwd_src_short(Items it, int64_t first, 
                                                        float* __restrict__ dh, int64_t ld_dh,
                                                        float* __restrict__ ds_src, int64_t ld_ds,
                                                        float* __restrict__ dz, HubMerge mg,
-                                                       const float* __restrict__ et) {
+                                                       const float* __restrict__ et, int gskip) {
   if (p > 0.f) seed = seed_in != nullptr ? *seed_in : epoch_seed(seed);
   constexpr int NV = C / 64;
   static_assert(NV >= 1, "k_bwd_src_short: C >= 64");
@@ -664,7 +675,7 @@ __global__ void __launch_bounds__(256) k_bwd_src_short(Items it, int64_t first, 
   const bool valid = k < re;
   const int i = valid ? row[k] : 0;
   float bg = 0.f, c1 = 0.f, c0 = 0.f;
-  int slot = 0;
+  int slot = 0, gi = valid ? i : -1;
   if (valid) {
     const float4 st = nstate[i];  // {s_dst, m, inv_l, D}
     float z = ss + st.x;
@@ -676,8 +687,9 @@ __global__ void __launch_bounds__(256) k_bwd_src_short(Items it, int64_t first, 
     const float a1 = af * dlogit(z, slope, mode);
     c1 = a1 * dm * gscale;
     c0 = a1 * st.w;
+    if (gskip && grow_unneeded(bg, c1, st.w)) gi = -1;
   }
-  rec[wv][lane] = make_int2(i, __float_as_int(bg));
+  rec[wv][lane] = make_int2(gi, __float_as_int(bg));  // dst row -1: no g_i needed, as k_bwd_src
   wave_sync();
   const int2* rq = &rec[wv][qr * 16];
   const int n = re - rs;
@@ -693,9 +705,10 @@ __global__ void __launch_bounds__(256) k_bwd_src_short(Items it, int64_t first, 
       const int t = t0 + u;
       const int2 r = rq[t & 15];
       bq[u] = t < n ? __int_as_float(r.y) : 0.f;
+      const bool need = r.x >= 0;  // (-1 past the item's last edge too)
 #pragma unroll
       for (int c = 0; c < NV; ++c)
-        g[u][c] = t < n ? ld4(grad_out + (int64_t)r.x * C + (ql + 16 * c) * 4) : f4(0.f);
+        g[u][c] = need ? ld4(grad_out + (int64_t)r.x * C + (ql + 16 * c) * 4) : f4(0.f);
     }
 #pragma unroll
     for (int u = 0; u < kSU; ++u) {
@@ -1172,6 +1185,13 @@ __global__ void __launch_bounds__(256) k_dst_merge(const int32_t* __restrict__ h
 
 static inline unsigned blocks_for(int64_t threads) { return (unsigned)((threads + 255) / 256); }
 
+// The gather-skip switch (include/ppgat.h ppgat_set_gather_skip), default on; each launch passes
+// the current value to the four edge kernels as an argument.  (The environment is not read here:
+// _lib.load applies PPGAT_GATHER_SKIP=0 once through the setter.)
+static std::atomic<int> g_gather_skip{1};
+int gather_skip() { return g_gather_skip.load(std::memory_order_relaxed); }
+int set_gather_skip(int on) { return g_gather_skip.exchange(on ? 1 : 0, std::memory_order_relaxed); }
+
 hipError_t launch_scores(const float* h, const float* as, const float* ad, int64_t n, int heads, int C, float* ss,
                          float* sd, hipStream_t st) {
   const int64_t pairs = n * heads;
@@ -1201,6 +1221,7 @@ hipError_t launch_fwd(const ppgat_schedule& sch, const int32_t* col, const int32
                       float eps, float p, uint64_t seed, uint64_t* seed_out, float* out, float* m, float* invl,
                       float* agg, float* partial, hipStream_t st, const float* et) {
   const float inv_keep = p > 0.f ? 1.f / (1.f - p) : 1.f;
+  const int gskip = gather_skip();
   // the effective mask seed is written by block 0 of the first edge kernel launched (no
   // separate launch); a graph without items snapshots it with k_seed_snap
   const int64_t n_long = short_begin(sch, heads, C);
@@ -1210,11 +1231,11 @@ hipError_t launch_fwd(const ppgat_schedule& sch, const int32_t* col, const int32
     if (et != nullptr) {
       PPGAT_DISPATCH_C(C, hipLaunchKernelGGL((k_fwd<CC, true>), dim3(blocks_for(n_long * 64)), dim3(256), 0, st, its,
                                              col, eid, heads, h, ss, sd, bias, mode, slope, eps, p, inv_keep, seed,
-                                             out, m, invl, agg, partial, seed_out, et));
+                                             out, m, invl, agg, partial, seed_out, et, gskip));
     } else {
       PPGAT_DISPATCH_C(C, hipLaunchKernelGGL(k_fwd<CC>, dim3(blocks_for(n_long * 64)), dim3(256), 0, st, its, col,
                                              eid, heads, h, ss, sd, bias, mode, slope, eps, p, inv_keep, seed, out, m,
-                                             invl, agg, partial, seed_out, et));
+                                             invl, agg, partial, seed_out, et, gskip));
     }
   }
   // the hub merges ride at the head of the short-item launch when there is one (one launch fewer)
@@ -1226,11 +1247,11 @@ hipError_t launch_fwd(const ppgat_schedule& sch, const int32_t* col, const int32
     if (et != nullptr)
       PPGAT_DISPATCH_C64(C, hipLaunchKernelGGL((k_fwd_short<CC, true>), dim3(g), dim3(256), 0, st, all, n_long, col,
                                                eid, h, ss, sd, bias, mode, slope, eps, p, inv_keep, seed, out, m, invl,
-                                               agg, n_long > 0 ? nullptr : seed_out, mg, et));
+                                               agg, n_long > 0 ? nullptr : seed_out, mg, et, gskip));
     else
       PPGAT_DISPATCH_C64(C, hipLaunchKernelGGL(k_fwd_short<CC>, dim3(g), dim3(256), 0, st, all, n_long, col, eid, h,
                                                ss, sd, bias, mode, slope, eps, p, inv_keep, seed, out, m, invl, agg,
-                                               n_long > 0 ? nullptr : seed_out, mg, et));
+                                               n_long > 0 ? nullptr : seed_out, mg, et, gskip));
   }
   if (sch.n_hubs > 0 && !fold) {
     PPGAT_DISPATCH_C(C, hipLaunchKernelGGL(k_fwd_merge<CC>, dim3(blocks_for(sch.n_hubs * 64)), dim3(256), 0, st,
@@ -1286,6 +1307,7 @@ hipError_t launch_bwd_src(const ppgat_schedule& sch, const int32_t* row, const i
                           float* dh, int64_t ld_dh, float* ds_src, int64_t ld_ds, float* dz, float* partial,
                           hipStream_t st, const float* et) {
   const float inv_keep = p > 0.f ? 1.f / (1.f - p) : 1.f;
+  const int gskip = gather_skip();
   const int64_t n_long = short_begin(sch, heads, C);
   const Items its = items_of(sch, n_long);
   if (n_long > 0) {
@@ -1310,12 +1332,14 @@ hipError_t launch_bwd_src(const ppgat_schedule& sch, const int32_t* row, const i
         PPGAT_DISPATCH_C(C, hipLaunchKernelGGL((k_bwd_src<CC, true>), dim3(blocks_for(n_long * 64)), dim3(256), 0, st,
                                                its, row, csc_eid, csc2csr, heads, h, ss,
                                                reinterpret_cast<const float4*>(nstate), go, mode, slope, gscale, p,
-                                               inv_keep, seed, seed_in, dh, ld_dh, ds_src, ld_ds, dz, partial, et));
+                                               inv_keep, seed, seed_in, dh, ld_dh, ds_src, ld_ds, dz, partial, et,
+                                               gskip));
       } else {
         PPGAT_DISPATCH_C(C, hipLaunchKernelGGL(k_bwd_src<CC>, dim3(blocks_for(n_long * 64)), dim3(256), 0, st, its,
                                                row, csc_eid, csc2csr, heads, h, ss,
                                                reinterpret_cast<const float4*>(nstate), go, mode, slope, gscale, p,
-                                               inv_keep, seed, seed_in, dh, ld_dh, ds_src, ld_ds, dz, partial, et));
+                                               inv_keep, seed, seed_in, dh, ld_dh, ds_src, ld_ds, dz, partial, et,
+                                               gskip));
       }
     }
   }
@@ -1329,12 +1353,12 @@ hipError_t launch_bwd_src(const ppgat_schedule& sch, const int32_t* row, const i
       PPGAT_DISPATCH_C64(C, hipLaunchKernelGGL((k_bwd_src_short<CC, true>), dim3(g), dim3(256), 0, st, all, n_long, row,
                                                csc_eid, csc2csr, h, ss, reinterpret_cast<const float4*>(nstate), go,
                                                mode, slope, gscale, p, inv_keep, seed, seed_in, dh, ld_dh, ds_src,
-                                               ld_ds, dz, mg, et));
+                                               ld_ds, dz, mg, et, gskip));
     else
       PPGAT_DISPATCH_C64(C, hipLaunchKernelGGL(k_bwd_src_short<CC>, dim3(g), dim3(256), 0, st, all, n_long, row,
                                                csc_eid, csc2csr, h, ss, reinterpret_cast<const float4*>(nstate), go,
                                                mode, slope, gscale, p, inv_keep, seed, seed_in, dh, ld_dh, ds_src,
-                                               ld_ds, dz, mg, et));
+                                               ld_ds, dz, mg, et, gskip));
   }
   if (sch.n_hubs > 0 && !fold) {
     PPGAT_DISPATCH_C(C, hipLaunchKernelGGL(k_bwd_merge<CC>, dim3(blocks_for(sch.n_hubs * 64)), dim3(256), 0, st,

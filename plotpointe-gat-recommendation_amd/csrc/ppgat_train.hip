@@ -444,7 +444,7 @@ __global__ void __launch_bounds__(256) k_bpr_chunks(const int32_t* __restrict__ 
             if (pon) {  // (uniform over the subgroup: its lanes share the segment)
               const float4 zr = make_float4(zd[k].x - bb.x, zd[k].y - bb.y, zd[k].z - bb.z, zd[k].w - bb.w);
               const float d = subgroup_dot<LPR>(acc, zr);
-              if (sl == 0) pro.nstate[r] = make_float4(ps[k], pm[k], pl[k], d * pro.gscale);
+              if (sl == 0) pro.nstate[r] = make_float4(ps[k], pm[k], pl[k], canon_d(d * pro.gscale, false));
             }
           }
           if (pon) bsum = add4(bsum, acc);
@@ -491,7 +491,9 @@ __global__ void __launch_bounds__(256) k_bpr_zero_untouched(const uint8_t* __res
   for (int64_t r = (int64_t)blockIdx.x * SPB + sg; r < n_rows; r += (int64_t)gridDim.x * SPB)
     if (!touched[r]) {
       st4(dZ + r * C + sl * 4, make_float4(0.f, 0.f, 0.f, 0.f));
-      if (pro.nstate != nullptr && sl == 0) pro.nstate[r] = make_float4(pro.sdst[r], pro.m[r], pro.invl[r], 0.f);
+      // D = -0.0f: the row is all zeros, pass B skips its gather (ppgat_device.h canon_d)
+      if (pro.nstate != nullptr && sl == 0)
+        pro.nstate[r] = make_float4(pro.sdst[r], pro.m[r], pro.invl[r], canon_d(0.f, true));
     }
 }
 
@@ -538,7 +540,7 @@ __global__ void __launch_bounds__(256) k_bpr_fixup(const int32_t* __restrict__ s
     const float4 bb = pro.bias ? ld4(pro.bias + sl * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
     const float4 zr = make_float4(zd.x - bb.x, zd.y - bb.y, zd.z - bb.z, zd.w - bb.w);
     const float d = subgroup_dot<LPR>(acc, zr);
-    if (sl == 0) pro.nstate[r] = make_float4(pro.sdst[r], pro.m[r], pro.invl[r], d * pro.gscale);
+    if (sl == 0) pro.nstate[r] = make_float4(pro.sdst[r], pro.m[r], pro.invl[r], canon_d(d * pro.gscale, false));
   }
 }
 
