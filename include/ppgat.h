@@ -499,6 +499,25 @@ int ppgat_adam_step_device(int count, float* const* params, const float* const* 
                            float* const* exp_avg_sq, const int64_t* numel, const float* const* step, double lr,
                            double beta1,
                            double beta2, float eps, float weight_decay, void* stream);
+/* Row-sparse ("lazy") Adam -- torch.optim.SparseAdam's place, with Adam's own rule: for each k in
+ * [0, n_rows), r = rows[k], ppgat_adam_step's element rule above on (param[r, c], grad_rows[k, c],
+ * exp_avg[r, c], exp_avg_sq[r, c]) for every column c, with one step_size and
+ * bias_correction2_sqrt for the table (its global step count).  param, exp_avg, exp_avg_sq:
+ * [n_table_rows, dim] contiguous; grad_rows [n_rows, dim]; rows [n_rows] int64.  Rows not named in
+ * rows are neither read nor written, so the update is lazy: untouched rows receive no momentum
+ * step, and weight decay acts on touched rows only.
+ * Contract: rows strictly ascending (hence unique: no two waves write one row) and inside
+ * [0, n_table_rows).  The kernel checks both as it goes and ORs into *flag (sticky; flag may be
+ * NULL): bit 1 = a row outside the range, which is skipped and never dereferenced; bit 2 =
+ * rows[k] <= rows[k - 1].  A raised flag means the step's result is invalid, never an
+ * out-of-bounds access.  The debug build validates the range of rows before the launch.
+ * Refused before any launch: a NULL param / exp_avg / exp_avg_sq / grad_rows / rows, dim < 1, a
+ * negative size -> PPGAT_ERR_INVALID; n_rows or n_table_rows >= 2^31 -> PPGAT_ERR_UNSUPPORTED.
+ * n_rows == 0: PPGAT_OK, nothing launched.  Traffic: 8 + 28 dim bytes per touched row.
+ * float4 accesses when dim % 4 == 0 and the four bases are 16-byte aligned.  Deterministic. */
+int ppgat_adam_rows(float* param, float* exp_avg, float* exp_avg_sq, const float* grad_rows, const int64_t* rows,
+                    int64_t n_rows, int64_t n_table_rows, int dim, float step_size, float bias_correction2_sqrt,
+                    double beta1, double beta2, float eps, float weight_decay, int* flag, void* stream);
 
 /* ---- replicated-item partition: cross-rank merge of item destination rows -----------------
  * Replaces: nothing one-to-one -- in the reference every destination's softmax sees all of

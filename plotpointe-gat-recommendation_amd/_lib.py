@@ -107,6 +107,8 @@ SIGNATURES = {
                                 c_f, c_f, c_vp]),
     "ppgat_adam_step_device": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_double, ctypes.c_double,
                                        ctypes.c_double, c_f, c_f, c_vp]),
+    "ppgat_adam_rows": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_f, c_f, ctypes.c_double,
+                                ctypes.c_double, c_f, c_f, c_vp, c_vp]),
     "ppgat_dropout_advance": (c_int, [c_vp]),
     "ppgat_set_gather_skip": (c_int, [c_int]),
     "ppgat_rep_merge": (c_int, [c_int, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -1033,6 +1033,24 @@ int ppgat_adam_step_device(int count, float* const* params, const float* const* 
   return PPGAT_OK;
 }
 
+int ppgat_adam_rows(float* param, float* exp_avg, float* exp_avg_sq, const float* grad_rows, const int64_t* rows,
+                    int64_t n_rows, int64_t n_table_rows, int dim, float step_size, float bias_correction2_sqrt,
+                    double beta1, double beta2, float eps, float weight_decay, int* flag, void* stream) {
+  if (n_rows < 0 || n_table_rows < 0 || dim < 1) return fail(PPGAT_ERR_INVALID, "adam_rows: bad sizes (dim >= 1)");
+  if (!param || !exp_avg || !exp_avg_sq || !grad_rows || !rows)
+    return fail(PPGAT_ERR_INVALID, "adam_rows: null pointer");
+  if (n_rows >= (int64_t)1 << 31 || n_table_rows >= (int64_t)1 << 31)
+    return fail(PPGAT_ERR_UNSUPPORTED, "adam_rows: n_rows and n_table_rows must be < 2^31");
+  if (n_rows == 0) return PPGAT_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = debug_range(rows, 8, n_rows, 0, n_table_rows, "adam_rows: rows", st)) return rc;
+  Timed t(PPGAT_K_ADAM, st);
+  hipError_t e = ppgat::adam_rows(param, exp_avg, exp_avg_sq, grad_rows, rows, n_rows, n_table_rows, dim, step_size,
+                                  bias_correction2_sqrt, beta1, beta2, eps, weight_decay, flag, st);
+  if (e != hipSuccess) return hip_fail(e, "adam_rows");
+  return PPGAT_OK;
+}
+
 int ppgat_rep_merge(int phase, const int32_t* item_rowptr, int64_t n_items, int heads, int channels, float* out,
                     float* agg, const float* bias, float* m, float* inv_l, float* mx, float* pack, void* stream) {
   if (phase < 0 || phase > 2) return fail(PPGAT_ERR_INVALID, "rep_merge: phase must be 0, 1 or 2");

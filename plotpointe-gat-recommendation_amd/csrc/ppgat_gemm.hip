@@ -18,6 +18,8 @@
 //  * k_wgrad: dW = G + att_src (x) G_s + att_dst (x) G_d and datt = W G_{s,d} (one launch).
 //  * k_adam: torch.optim.Adam's update (L2 weight decay, bias corrections; the arithmetic of
 //    ATen's fused Adam) over up to 16 tensors per launch.
+//  * k_adam_rows: the same element rule on the named rows of one table alone (row-sparse,
+//    lazy Adam: untouched rows get neither momentum nor weight decay).
 //
 // MFMA: v_mfma_f32_16x16x4_f32 (projections) and v_mfma_f32_32x32x2_f32 (k_tn128), exact
 // fp32 FMA chains (MI355X_MICROARCH.md: 157 TF peak; 32 / 64 cycles per instruction per
@@ -697,6 +699,66 @@ __global__ void __launch_bounds__(256) k_adam(AdamArg a) {
         M[x] = m;
         V[x] = v;
       }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Row-sparse ("lazy") Adam: k_adam's element rule (adam_elem, the one definition) on the
+// rows named in rows[0 .. n_rows) of a [n_table, dim] table, gradient row k for table row
+// rows[k]; no other row is read or written, so momentum and weight decay act on touched
+// rows only.  L = 1 << lgL lanes own one row (64 / L rows per wave); a lane takes four
+// consecutive columns per trip and strides by 4 L (more than one trip when dim > 256).
+// vec (dim % 4 == 0 and 16-byte bases, decided by the launcher -- the split k_adam makes):
+// float4 loads and stores; otherwise the same four columns one float at a time, bounded by
+// dim.  Both feed ONE copy of the arithmetic, so an unaligned table gets the aligned one's
+// bits.  The contract on rows is strict ascent inside [0, n_table): checked here as the
+// kernel goes (the lanes of row k also read rows[k - 1]); a row outside the range is
+// skipped, never dereferenced (flag bit 1), a row <= its predecessor raises bit 2 (two
+// waves may then have written one row: the step is invalid, every access still in bounds).
+// flag (nullable) is only ever OR'd.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+k_adam_rows(float* __restrict__ P, float* __restrict__ M, float* __restrict__ V, const float* __restrict__ G,
+            const int64_t* __restrict__ rows, int64_t n_rows, int64_t n_table, int dim, int lgL, int vec, float ss,
+            float bc, float beta1, float beta2, float omb1, float omb2, float eps, float wd, int* __restrict__ flag) {
+  const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t k = gid >> lgL;
+  if (k >= n_rows) return;
+  const int L = 1 << lgL, sub = (int)(gid & (L - 1));
+  const int64_t r = rows[k];
+  int bits = (r < 0 || r >= n_table) ? 1 : 0;
+  if (k > 0 && r <= rows[k - 1]) bits |= 2;
+  if (bits != 0 && flag != nullptr && sub == 0) atomicOr(flag, bits);
+  if (bits & 1) return;
+  float* __restrict__ p_ = P + r * dim;
+  float* __restrict__ m_ = M + r * dim;
+  float* __restrict__ v_ = V + r * dim;
+  const float* __restrict__ g_ = G + k * dim;
+  for (int c = sub * 4; c < dim; c += L * 4) {
+    float4 p, g, m, v;
+    if (vec) {
+      p = ld4(p_ + c), g = ld4(g_ + c), m = ld4(m_ + c), v = ld4(v_ + c);
+    } else {  // columns past dim: harmless values, computed and dropped
+      p = f4(0.f), g = f4(0.f), m = f4(0.f), v = f4(1.f);
+      p.x = p_[c], g.x = g_[c], m.x = m_[c], v.x = v_[c];
+      if (c + 1 < dim) p.y = p_[c + 1], g.y = g_[c + 1], m.y = m_[c + 1], v.y = v_[c + 1];
+      if (c + 2 < dim) p.z = p_[c + 2], g.z = g_[c + 2], m.z = m_[c + 2], v.z = v_[c + 2];
+      if (c + 3 < dim) p.w = p_[c + 3], g.w = g_[c + 3], m.w = m_[c + 3], v.w = v_[c + 3];
+    }
+    adam_elem(p.x, g.x, m.x, v.x, beta1, beta2, omb1, omb2, eps, wd, ss, bc);
+    adam_elem(p.y, g.y, m.y, v.y, beta1, beta2, omb1, omb2, eps, wd, ss, bc);
+    adam_elem(p.z, g.z, m.z, v.z, beta1, beta2, omb1, omb2, eps, wd, ss, bc);
+    adam_elem(p.w, g.w, m.w, v.w, beta1, beta2, omb1, omb2, eps, wd, ss, bc);
+    if (vec) {
+      st4(p_ + c, p);
+      st4(m_ + c, m);
+      st4(v_ + c, v);
+    } else {
+      p_[c] = p.x, m_[c] = m.x, v_[c] = v.x;
+      if (c + 1 < dim) p_[c + 1] = p.y, m_[c + 1] = m.y, v_[c + 1] = v.y;
+      if (c + 2 < dim) p_[c + 2] = p.z, m_[c + 2] = m.z, v_[c + 2] = v.z;
+      if (c + 3 < dim) p_[c + 3] = p.w, m_[c + 3] = m.w, v_[c + 3] = v.w;
     }
   }
 }
@@ -1775,6 +1837,22 @@ hipError_t adam_step(int count, float* const* p, const float* const* g, float* c
   }
   if (blocks == 0) return hipSuccess;
   hipLaunchKernelGGL(k_adam, dim3((unsigned)blocks), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// n_rows, n_table < 2^31 (the ABI refuses more): at most 2^37 lanes, 2^29 blocks
+hipError_t adam_rows(float* p, float* m, float* v, const float* g, const int64_t* rows, int64_t n_rows,
+                     int64_t n_table, int dim, float step_size, float bc2_sqrt, double beta1, double beta2, float eps,
+                     float wd, int* flag, hipStream_t st) {
+  if (n_rows == 0) return hipSuccess;
+  int lgL = 0;  // lanes per row: min(64, the power of two >= ceil(dim / 4))
+  while (lgL < 6 && (1 << lgL) < (dim + 3) / 4) ++lgL;
+  const int64_t blocks = ((n_rows << lgL) + 255) / 256;
+  const bool vec = dim % 4 == 0 && ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) |
+                                     reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 15) == 0;
+  const float b1 = (float)beta1, b2 = (float)beta2, omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
+  hipLaunchKernelGGL(k_adam_rows, dim3((unsigned)blocks), dim3(256), 0, st, p, m, v, g, rows, n_rows, n_table, dim, lgL,
+                     vec ? 1 : 0, step_size, bc2_sqrt, b1, b2, omb1, omb2, eps, wd, flag);
   return hipGetLastError();
 }
 

@@ -157,6 +157,10 @@ hipError_t rows_return_add(float* dst, int64_t ldd, const float* ret, int64_t ld
 hipError_t adam_step(int count, float* const* p, const float* const* g, float* const* m, float* const* v,
                      const int64_t* n, const float* step_size, const float* bc2_sqrt, double beta1, double beta2,
                      float eps, float wd, const float* const* tstep, double lr, hipStream_t st);
+// row-sparse Adam: adam_step's element rule on rows[0 .. n_rows) of a [n_table, dim] table (ppgat_gemm.hip)
+hipError_t adam_rows(float* p, float* m, float* v, const float* g, const int64_t* rows, int64_t n_rows,
+                     int64_t n_table, int dim, float step_size, float bc2_sqrt, double beta1, double beta2, float eps,
+                     float wd, int* flag, hipStream_t st);
 
 // I-I kNN neighbour selection (ppgat_knn.hip)
 int knn_max_k();

@@ -1289,6 +1289,32 @@ def join_rows(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return _JoinRows.apply(a, b) if rows_adjacent(a, b) else torch.cat([a, b], 0)
 
 
+class _EmbeddingRows(torch.autograd.Function):
+    """weight.index_select(0, idx) whose gradient for ``weight`` is row-sparse: a COO tensor with
+    ``idx`` as its one sparse dimension and the incoming rows as its values -- no zero-filled
+    [n_rows, d] gradient.  Not flagged coalesced: repeated ids in ``idx`` stay separate entries
+    (they add on coalesce(), as index_select's backward adds them)."""
+
+    @staticmethod
+    def forward(ctx, weight, idx):
+        ctx.save_for_backward(idx)
+        ctx.shape = weight.shape
+        return weight.index_select(0, idx)
+
+    @staticmethod
+    def backward(ctx, g):
+        (idx,) = ctx.saved_tensors
+        return torch.sparse_coo_tensor(idx[None], g.contiguous(), ctx.shape), None
+
+
+def embedding_rows(weight: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """``weight.index_select(0, idx)`` for a 2-D table and int64 ``idx``, with a row-sparse gradient
+    (``optim.Adam`` takes it: the lazy row step).  Pure torch on any device; launches no kernel."""
+    _require(weight.dim() == 2 and idx.dim() == 1 and idx.dtype == torch.int64,
+             "embedding_rows: weight [n, d] and int64 idx [k] expected")
+    return _EmbeddingRows.apply(weight, idx)
+
+
 # ---------------------------------------------------------------------------
 # general fp32 matrix-core GEMMs (include/ppgat.h ppgat_gemm_nn / ppgat_gemm_tn_big)
 # ---------------------------------------------------------------------------

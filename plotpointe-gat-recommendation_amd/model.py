@@ -91,7 +91,7 @@ def _stack(model, item_proj, item_feats, layers, edge_index, edge_attr=None):
     return x
 
 
-def forward_subgraph(model, item_feats, sub, edge_attr=None):
+def forward_subgraph(model, item_feats, sub, edge_attr=None, sparse_grad=False):
     """The layer stack on a ``neighbors.Subgraph``: ``Z_s [N_s, d]``, row k the embedding of node
     ``sub.n_id[k]`` (exact at the seeds when ``hops`` = the number of layers: a seed's output reads
     its sampled neighbourhood to that depth and no further).  Only the subgraph's nodes are touched:
@@ -99,10 +99,16 @@ def forward_subgraph(model, item_feats, sub, edge_attr=None):
     the subgraph's items alone -- the node-side saving -- and the node table of ``_stack`` is not
     used.  The embedding gradient arrives through ``index_select``'s backward; ``n_id`` is unique,
     so each row is added once.  ``edge_attr``: the PARENT graph's [E, D] tensor, gathered by
-    ``sub.eid`` here."""
+    ``sub.eid`` here.  ``sparse_grad=True``: the user rows come from ``hip_ops.embedding_rows``, whose
+    gradient for ``user_emb.weight`` is row-sparse over ``n_id[:n_users_s]`` (no zero-filled
+    [n_users, d] gradient) -- for ``optim.Adam``'s lazy row step.  ``n_id`` is V ascending, so those
+    indices are strictly ascending and in range: ``optim.Adam(rows="ascending")`` is sound for them."""
     layers = model.convs if hasattr(model, "convs") else model.layers
     nu = sub.n_users_s
-    xu = model.user_emb.weight.index_select(0, sub.n_id[:nu])
+    if sparse_grad:
+        xu = hip_ops.embedding_rows(model.user_emb.weight, sub.n_id[:nu])
+    else:
+        xu = model.user_emb.weight.index_select(0, sub.n_id[:nu])
     if sub.n_nodes > nu:
         feats = item_feats.index_select(0, sub.n_id[nu:] - model.n_users)
         xv = hip_ops.linear(feats, model.item_proj.weight, model.item_proj.bias)
@@ -168,9 +174,9 @@ class PyGGAT(torch.nn.Module):
     def forward(self, item_feats: torch.Tensor, edge_index: torch.Tensor, edge_attr=None) -> torch.Tensor:
         return _stack(self, self.item_proj, item_feats, self.convs, edge_index, edge_attr)
 
-    def forward_subgraph(self, item_feats: torch.Tensor, sub, edge_attr=None) -> torch.Tensor:
+    def forward_subgraph(self, item_feats: torch.Tensor, sub, edge_attr=None, sparse_grad=False) -> torch.Tensor:
         """``Z_s [N_s, hidden]`` on a ``neighbors.Subgraph`` (model.forward_subgraph)."""
-        return forward_subgraph(self, item_feats, sub, edge_attr)
+        return forward_subgraph(self, item_feats, sub, edge_attr, sparse_grad)
 
     def attention(self, item_feats: torch.Tensor, edge_index: torch.Tensor, edge_attr=None, order: str = "edge"):
         """One [E, H] attention tensor per layer (layer_attention)."""
@@ -202,11 +208,11 @@ class PyGGATv2(torch.nn.Module):
     def forward(self, item_feats: torch.Tensor, edge_index: torch.Tensor) -> torch.Tensor:
         return _stack(self, self.item_proj, item_feats, self.convs, edge_index)
 
-    def forward_subgraph(self, item_feats: torch.Tensor, sub, edge_attr=None) -> torch.Tensor:
+    def forward_subgraph(self, item_feats: torch.Tensor, sub, edge_attr=None, sparse_grad=False) -> torch.Tensor:
         """``Z_s [N_s, hidden]`` on a ``neighbors.Subgraph`` (model.forward_subgraph); no ``edge_attr``."""
         if edge_attr is not None:
             raise NotImplementedError("PyGGATv2: edge features are not implemented")
-        return forward_subgraph(self, item_feats, sub)
+        return forward_subgraph(self, item_feats, sub, sparse_grad=sparse_grad)
 
     def attention(self, item_feats: torch.Tensor, edge_index: torch.Tensor, edge_attr=None, order: str = "edge"):
         """One [E, H] attention tensor per layer (layer_attention); GATv2Conv takes no ``edge_attr``."""
@@ -233,11 +239,11 @@ class CustomGAT(torch.nn.Module):
     def forward(self, item_feats: torch.Tensor, edge_index: torch.Tensor) -> torch.Tensor:
         return _stack(self, self.item_proj, item_feats, self.layers, edge_index)
 
-    def forward_subgraph(self, item_feats: torch.Tensor, sub, edge_attr=None) -> torch.Tensor:
+    def forward_subgraph(self, item_feats: torch.Tensor, sub, edge_attr=None, sparse_grad=False) -> torch.Tensor:
         """``Z_s [N_s, hidden]`` on a ``neighbors.Subgraph`` (model.forward_subgraph); no ``edge_attr``."""
         if edge_attr is not None:
             raise NotImplementedError("CustomGAT: edge features are not implemented")
-        return forward_subgraph(self, item_feats, sub)
+        return forward_subgraph(self, item_feats, sub, sparse_grad=sparse_grad)
 
     def attention(self, item_feats: torch.Tensor, edge_index: torch.Tensor, edge_attr=None, order: str = "edge"):
         """One [E, 1] attention tensor per layer (layer_attention); the custom layer takes no ``edge_attr``."""

@@ -258,13 +258,21 @@ def check_subgraph_batch(args):
         raise ValueError("--subgraph-batch draws a sample per batch: --resample-every must stay 1")
 
 
+def check_sparse_adam(args):
+    """--sparse-adam (optim.Adam's lazy row step on the user table, fed by forward_subgraph's
+    row-sparse gradient) is the optimiser of the mini-batch trainer: it needs --subgraph-batch > 0."""
+    if args.sparse_adam and args.subgraph_batch <= 0:
+        raise ValueError("--sparse-adam needs --subgraph-batch > 0: only a mini-batch step leaves user rows untouched")
+
+
 def subgraph_epoch(model, opt, item_feats, sub_sampler, epoch: int, batch: int, n_users: int, u, i, j,
-                   loss: str = "bpr", edge_attr=None, softmax=None):
+                   loss: str = "bpr", edge_attr=None, softmax=None, sparse_grad: bool = False):
     """One epoch of mini-batch steps on seed subgraphs.  The epoch's triples (or ``softmax`` =
     (cand [S, M + 1], temperature[, logQ table by global item id])) are cut in order into
     ceil(S / batch) batches; per batch the seeds are its users and ``n_users +`` its items, the
     subgraph is ``sub_sampler.batch(epoch - 1, b, seeds)``, and forward, loss (on ``seed_local``:
     the seeds' local ids in the seeds' order), zero_grad, backward and ``opt.step()`` run on it.
+    ``sparse_grad``: the user table's gradient is row-sparse over the batch's users (--sparse-adam).
     Returns (the sample-weighted mean loss, a 0-d tensor; batches; mean nodes; mean edges)."""
     S = int(u.numel())
     n_batches = (S + batch - 1) // batch
@@ -281,7 +289,7 @@ def subgraph_epoch(model, opt, item_feats, sub_sampler, epoch: int, batch: int, 
         sub = sub_sampler.batch(epoch - 1, b, torch.cat([u[lo_:hi_], items + n_users]))
         nus = sub.n_users_s
         ul, il = sub.seed_local[:s].contiguous(), sub.seed_local[s:] - nus
-        Z = model.forward_subgraph(item_feats, sub, edge_attr)
+        Z = model.forward_subgraph(item_feats, sub, edge_attr, sparse_grad=sparse_grad)
         if softmax is not None:
             corr_s = corr[0].index_select(0, sub.n_id[nus:] - n_users) if corr else None
             lo = model_mod.softmax_loss(Z, nus, ul, il.view(s, -1), temperature, correction=corr_s)
@@ -666,6 +674,9 @@ def build_parser():
                     help="--fanout: cut the epoch's triples into batches of B and take one optimiser step per batch, "
                          "on the --layers-hop sampled subgraph of the batch's users and items alone (0 = off: one "
                          "step per epoch).  Evaluation and the exports keep the whole graph.  GAT families, one GPU")
+    ap.add_argument("--sparse-adam", action="store_true",
+                    help="--subgraph-batch: lazy row-sparse Adam on the user table (ppgat_adam_rows): each batch "
+                         "updates its own user rows alone; untouched rows get no momentum step and no weight decay")
     return ap
 
 
@@ -674,6 +685,7 @@ def main(argv=None):
     check_edge_features(args)
     check_softmax_loss(args)
     check_subgraph_batch(args)
+    check_sparse_adam(args)
     check_fanout(args)
     logq = check_negative_sampling(args)
     if args.recommend_out and args.world_size > 1:
@@ -760,7 +772,10 @@ def main(argv=None):
         opt = torch.optim.Adam(sharded.parameters(), lr=cfg.lr, weight_decay=cfg.l2)
     else:
         eval_model = model
-        opt = torch.optim.Adam(model.parameters(), lr=cfg.lr, weight_decay=cfg.l2)
+        if args.sparse_adam:  # n_id is ascending (neighbors.Subgraph): no sort per batch
+            opt = optim_mod.Adam(model.parameters(), lr=cfg.lr, weight_decay=cfg.l2, rows="ascending")
+        else:
+            opt = torch.optim.Adam(model.parameters(), lr=cfg.lr, weight_decay=cfg.l2)
     out_dir = _local(cfg.models_prefix)
     (out_dir / "checkpoints").mkdir(parents=True, exist_ok=True)
     best_path = out_dir / "checkpoints" / f"{run_id}.pt"
@@ -814,8 +829,11 @@ def main(argv=None):
                     softmax += (ssm_corr,)
             if sub_sampler is not None:
                 lo, *sub_stats = subgraph_epoch(model, opt, item_feats, sub_sampler, epoch, args.subgraph_batch,
-                                                n_users, u, i, j, cfg.loss, edge_attr=edge_attr, softmax=softmax)
+                                                n_users, u, i, j, cfg.loss, edge_attr=edge_attr, softmax=softmax,
+                                                sparse_grad=args.sparse_adam)
                 loss_val = float(lo.item())
+                if args.sparse_adam:  # the loss is on the host: the row-contract flag costs no wait of its own
+                    opt.check_rows()
             else:
                 loss_val = float(epoch_step(model, opt, item_feats, step_edges, n_users, u, i, j, cfg.loss,
                                             edge_attr=step_attr, softmax=softmax, shared=shared).item())
@@ -879,6 +897,9 @@ def main(argv=None):
     if sub_sampler is not None:
         out["notes"] += (f"; --subgraph-batch {args.subgraph_batch}: one optimiser step per batch of triples, on the "
                          f"{cfg.layers}-hop fan-out {args.fanout} subgraph of the batch's users and items")
+    if args.sparse_adam:
+        out["notes"] += ("; --sparse-adam: lazy row-sparse Adam on the user table -- user rows outside a batch's "
+                         "subgraph are untouched by its step: no momentum coasting and no weight decay for them")
     if full:
         out["config"] = {**cfg.__dict__, "eval_mode": "full"}
         out["notes"] += "; " + FULL_EVAL_NOTE
