@@ -38,7 +38,7 @@ import math
 
 import torch
 
-from . import _lib
+from . import _launch, _lib
 from .hip_ops import (EDGE_MAX_DIM, check_edge_attr, gat_layer, gat_layer_attention, gatv2_aggregate,
                       gatv2_layer_attention, gatv2_supported, graph_cache, join_rows, linear)
 
@@ -76,7 +76,7 @@ class GATConv(torch.nn.Module):
             edge_dim = int(edge_dim)
         if residual:
             raise NotImplementedError("residual=True not implemented")
-        if not _lib.load().ppgat_supported_channels(int(out_channels)):
+        if not _launch.supported_channels(out_channels):
             raise NotImplementedError(f"out_channels={out_channels}: fused kernels take C in 4*2^k <= 256")
         if heads > 8:
             raise NotImplementedError("heads > 8 not implemented")
@@ -272,7 +272,7 @@ class SimpleGATLayer(torch.nn.Module):
 
     def __init__(self, in_dim: int, out_dim: int, attn_dropout: float = 0.1):
         super().__init__()
-        if not _lib.load().ppgat_supported_channels(int(out_dim)):
+        if not _launch.supported_channels(out_dim):
             raise NotImplementedError(f"out_dim={out_dim}: fused kernels take C in 4*2^k <= 256")
         # creation/initialisation order identical to the reference (RNG-consuming calls)
         self.lin = torch.nn.Linear(in_dim, out_dim, bias=False)

@@ -25,14 +25,13 @@
 """
 from __future__ import annotations
 
-import ctypes
 import math
 from typing import Dict, Sequence
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _launch
 
 
 def sample_eval_candidates(train_pos_idx: Dict[int, np.ndarray], eval_pos: Dict[int, int], n_items: int,
@@ -75,7 +74,6 @@ def sample_eval_candidates_fast(train_pos_idx: Dict[int, np.ndarray], eval_pos: 
 
 def sampled_rank(Z: torch.Tensor, n_users: int, users: np.ndarray, cands: np.ndarray, row_map=None) -> np.ndarray:
     """rank[b] = #(scores > positive score) + 1 for candidate lists (column 0 = positive)."""
-    lib = _lib.load()
     if not Z.is_cuda or Z.dtype != torch.float32:
         raise RuntimeError("sampled_rank: fp32 ROCm tensor required (no CPU path)")
     Z = Z.contiguous()
@@ -85,9 +83,7 @@ def sampled_rank(Z: torch.Tensor, n_users: int, users: np.ndarray, cands: np.nda
     u = torch.as_tensor(users, dtype=torch.int64).to(dev).contiguous()
     c = torch.as_tensor(cands, dtype=torch.int64).to(dev).contiguous()
     rank = torch.empty(len(u), dtype=torch.int32, device=dev)
-    _lib.check(lib.ppgat_sampled_rank(Z.data_ptr(), n_rows, n_users, n_items, _lib.ptr(row_map), C, u.data_ptr(),
-                                      c.data_ptr(), len(u), c.size(1), rank.data_ptr(), _lib.stream_handle(dev)),
-               "sampled_rank")
+    _launch.sampled_rank(Z, n_users, n_items, row_map, u, c, rank)
     return rank.cpu().numpy()
 
 
@@ -142,16 +138,12 @@ def full_rank(Z_users: torch.Tensor, Z_items: torch.Tensor, users, pos, sampler=
     excluded set); None = nothing but the positive is excluded.  ``return_ties`` adds the count
     of non-excluded items whose score EQUALS the positive's (a collapsed model shows there: the
     strict rule ranks every user first when all scores are equal)."""
-    lib = _lib.load()
     for t in (Z_users, Z_items):
         if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2:
             raise RuntimeError("full_rank: 2-D fp32 ROCm tensors required (no CPU path)")
     if Z_users.size(1) != Z_items.size(1) or Z_users.device != Z_items.device:
         raise ValueError("full_rank: Z_users and Z_items differ in width or device")
     dev = Z_users.device
-    C = Z_users.size(1)
-    up, ldu = _lib.row_ptr(Z_users)
-    ip, ldi = _lib.row_ptr(Z_items)
     u = torch.as_tensor(users, dtype=torch.int64).to(dev).contiguous()
     p = torch.as_tensor(pos, dtype=torch.int64).to(dev).contiguous()
     if u.shape != p.shape or u.dim() != 1:
@@ -161,13 +153,8 @@ def full_rank(Z_users: torch.Tensor, Z_items: torch.Tensor, users, pos, sampler=
     n = u.numel()
     rank = torch.empty(n, dtype=torch.int32, device=dev)
     ties = torch.empty(n, dtype=torch.int32, device=dev) if return_ties else None
-    ws, nbytes = _lib.workspace(lib.ppgat_full_rank_workspace_bytes, n, Z_items.size(0), C, device=dev)
-    _lib.check(lib.ppgat_full_rank(up, ldu, Z_users.size(0), ip, ldi, Z_items.size(0), C, _lib.ptr(u) if n else None,
-                                   _lib.ptr(p) if n else None, n,
-                                   None if sampler is None else sampler.ptr.data_ptr(),
-                                   None if sampler is None else sampler.items.data_ptr(),
-                                   rank.data_ptr() if n else None, _lib.ptr(ties) if n else None,
-                                   ws.data_ptr() if nbytes else None, nbytes, _lib.stream_handle(dev)), "full_rank")
+    _launch.full_rank(Z_users, Z_items, u, p, None if sampler is None else sampler.ptr,
+                      None if sampler is None else sampler.items, rank, ties)
     if return_ties:
         return rank.cpu().numpy(), ties.cpu().numpy()
     return rank.cpu().numpy()
@@ -208,16 +195,12 @@ def recommend_topk(Z_users: torch.Tensor, Z_items: torch.Tensor, users=None, k: 
     and ``sampler`` as in ``full_rank``: row or column views of one node table are used in place,
     the sampler's sorted history CSR is the excluded set (None = nothing is excluded).  One fused
     matrix-core pass (``ppgat_full_topk``): the ``[users, items]`` score matrix is never written."""
-    lib = _lib.load()
     for t in (Z_users, Z_items):
         if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2:
             raise RuntimeError("recommend_topk: 2-D fp32 ROCm tensors required (no CPU path)")
     if Z_users.size(1) != Z_items.size(1) or Z_users.device != Z_items.device:
         raise ValueError("recommend_topk: Z_users and Z_items differ in width or device")
     dev = Z_users.device
-    C = Z_users.size(1)
-    up, ldu = _lib.row_ptr(Z_users)
-    ip, ldi = _lib.row_ptr(Z_items)
     u = None
     if users is not None:
         u = torch.as_tensor(users, dtype=torch.int64).to(dev).contiguous()
@@ -229,13 +212,8 @@ def recommend_topk(Z_users: torch.Tensor, Z_items: torch.Tensor, users=None, k: 
     k = int(k)
     idx = torch.empty(n, k, dtype=torch.int32, device=dev)
     sc = torch.empty(n, k, dtype=torch.float32, device=dev) if return_scores else None
-    ws, nbytes = _lib.workspace(lib.ppgat_full_topk_workspace_bytes, n, Z_items.size(0), C, k, device=dev)
-    _lib.check(lib.ppgat_full_topk(up, ldu, Z_users.size(0), ip, ldi, Z_items.size(0), C,
-                                   _lib.ptr(u) if n else None, n,
-                                   None if sampler is None else sampler.ptr.data_ptr(),
-                                   None if sampler is None else sampler.items.data_ptr(), k,
-                                   idx.data_ptr() if n else None, _lib.ptr(sc) if n else None,
-                                   ws.data_ptr() if nbytes else None, nbytes, _lib.stream_handle(dev)), "full_topk")
+    _launch.full_topk(Z_users, Z_items, u, n, None if sampler is None else sampler.ptr,
+                      None if sampler is None else sampler.items, k, idx, sc)
     return (idx, sc) if return_scores else idx
 
 
@@ -360,7 +338,6 @@ def top_k_batch(item_vecs: torch.Tensor, histories: Sequence[Sequence[int]], k: 
     """serving/runtime.py:56-76 for a batch of users on the device (ppgat_serve_topk): per
     history, the mean of its rows, scores over every item, the history masked to -1e9, the
     k best descending (ties by smaller index).  Returns (indices [B, k] int64, scores [B, k])."""
-    lib = _lib.load()
     if not item_vecs.is_cuda or item_vecs.dtype != torch.float32:
         raise RuntimeError("top_k_batch: fp32 ROCm item vectors required (no CPU path)")
     iv = item_vecs.contiguous()
@@ -375,14 +352,10 @@ def top_k_batch(item_vecs: torch.Tensor, histories: Sequence[Sequence[int]], k: 
         ptr = torch.from_numpy(np.concatenate([[0], np.cumsum(lens)])).to(dev)
         hist = torch.from_numpy(np.concatenate([np.asarray(h, np.int64) for h in chunk])).to(dev)
         B = len(chunk)
-        nbytes = ctypes.c_size_t(0)
-        _lib.check(lib.ppgat_serve_topk_workspace_bytes(n_items, C, B, ctypes.byref(nbytes)), "serve_topk_ws")
-        ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev)
+        ws, nbytes = _launch.serve_topk_workspace(n_items, C, B, dev)
         oi = torch.empty(B, k, dtype=torch.int32, device=dev)
         os_ = torch.empty(B, k, dtype=torch.float32, device=dev)
-        _lib.check(lib.ppgat_serve_topk(iv.data_ptr(), n_items, C, ptr.data_ptr(), hist.data_ptr(), int(lens.max()), B,
-                                        int(k), oi.data_ptr(), os_.data_ptr(), ws.data_ptr(), nbytes.value,
-                                        _lib.stream_handle(dev)), "serve_topk")
+        _launch.serve_topk(iv, ptr, hist, int(lens.max()), B, int(k), oi, os_, ws, nbytes)
         idx_out.append(oi.long())
         sc_out.append(os_)
     return torch.cat(idx_out), torch.cat(sc_out)

@@ -21,21 +21,19 @@ embeddings/fuse_modal.py.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Dict, Optional
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _launch
 from . import hip_ops
 
 
 def fusion_forward(txt: torch.Tensor, img: Optional[torch.Tensor], W1, b1, W2, b2, normalize: bool,
                    img_index: Optional[torch.Tensor] = None, img_fallback: Optional[torch.Tensor] = None,
                    want_z1: bool = False):
-    lib = _lib.load()
     if not txt.is_cuda or txt.dtype != torch.float32:
         raise RuntimeError("fusion_forward: fp32 ROCm tensors required (no CPU path)")
     dev = txt.device
@@ -45,19 +43,12 @@ def fusion_forward(txt: torch.Tensor, img: Optional[torch.Tensor], W1, b1, W2, b
     H1, Do = W1.size(0), W2.size(0)
     out = torch.empty(n, Do, dtype=torch.float32, device=dev)
     z1 = torch.empty(n, H1, dtype=torch.float32, device=dev) if want_z1 else None
-    ptr = _lib.ptr
     # keep every converted tensor alive until the launch is enqueued
     imgc = img.contiguous() if img is not None else None
     idx32 = img_index.to(torch.int32).contiguous() if img_index is not None else None
     fb = img_fallback.contiguous() if img_fallback is not None else None
     W1c, b1c, W2c, b2c = (t.detach().contiguous() for t in (W1, b1, W2, b2))
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(lib.ppgat_fusion_fwd_workspace_bytes(Dt, Di, H1, Do, ctypes.byref(nbytes)), "fusion_fwd_workspace")
-    ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev)  # the pre-split W1 / W2 images
-    _lib.check(lib.ppgat_fusion_fwd_ws(ptr(txt), ptr(imgc), ptr(idx32), ptr(fb), n, Dt, Di, W1c.data_ptr(),
-                                       b1c.data_ptr(), H1, W2c.data_ptr(), b2c.data_ptr(), Do, 1 if normalize else 0,
-                                       out.data_ptr(), ptr(z1), ws.data_ptr(), nbytes.value, _lib.stream_handle(dev)),
-               "fusion_fwd")
+    _launch.fusion_fwd(txt, imgc, idx32, fb, Di, W1c, b1c, W2c, b2c, normalize, out, z1)
     return (out, z1) if want_z1 else out
 
 
@@ -116,37 +107,29 @@ def contrastive_fusion_loss(fused, txt_emb, img_emb, temperature=0.07):
 def infonce(fused: torch.Tensor, txt_p: torch.Tensor, img_p: torch.Tensor, temperature: float = 0.07):
     """contrastive_fusion_loss forward and gradient on the device (ppgat_infonce) ->
     (loss [3] = {loss, loss_txt, loss_img}, d_fused, d_txt_p, d_img_p)."""
-    lib = _lib.load()
     for name, t in (("fused", fused), ("txt_p", txt_p), ("img_p", img_p)):
         if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous()):
             raise RuntimeError(f"infonce: {name} must be a contiguous fp32 ROCm [B, D] tensor (no CPU path)")
     B, D = fused.shape
     if txt_p.shape != (B, D) or img_p.shape != (B, D):
         raise ValueError("infonce: fused, txt_p, img_p must share [B, D]")
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(lib.ppgat_infonce_workspace_bytes(B, D, ctypes.byref(nbytes)), "infonce_workspace_bytes")
     dev = fused.device
-    ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev)
+    ws, nbytes = _launch.infonce_workspace(B, D, dev)
     loss = torch.empty(3, dtype=torch.float32, device=dev)
     dF, dT, dI = (torch.empty(B, D, dtype=torch.float32, device=dev) for _ in range(3))
-    _lib.check(lib.ppgat_infonce(fused.data_ptr(), txt_p.data_ptr(), img_p.data_ptr(), B, D, float(temperature),
-                                 loss.data_ptr(), dF.data_ptr(), dT.data_ptr(), dI.data_ptr(), ws.data_ptr(),
-                                 nbytes.value, _lib.stream_handle(dev)), "infonce")
+    _launch.infonce(fused, txt_p, img_p, temperature, loss, dF, dT, dI, ws, nbytes)
     return loss, dF, dT, dI
 
 
 def relu_dropout(z: torch.Tensor, p: float, seed: int, grad: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Forward (grad None): relu(z) * mask.  Backward: grad * mask * [z > 0], in place on grad.
     The mask is a counter hash of (seed, element) (ppgat_relu_dropout), identical both ways."""
-    lib = _lib.load()
     if not (z.is_cuda and z.dtype == torch.float32 and z.is_contiguous()):
         raise RuntimeError("relu_dropout: contiguous fp32 ROCm tensor required (no CPU path)")
     out = torch.empty_like(z) if grad is None else grad
     if grad is not None and (grad.shape != z.shape or not grad.is_contiguous()):
         raise ValueError("relu_dropout: grad must be contiguous and shaped like z")
-    _lib.check(lib.ppgat_relu_dropout(z.data_ptr(), z.numel(), float(p), _lib.seed64(seed),
-                                      0 if grad is None else 1, out.data_ptr(), _lib.stream_handle(z.device)),
-               "relu_dropout")
+    _launch.relu_dropout(z, p, seed, grad is not None, out)
     return out
 
 

@@ -23,16 +23,15 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib
+from . import _launch
 from . import hip_ops
 
 
 def build_ii_knn(embeddings: torch.Tensor, k: int = 20, min_similarity: float = 0.3, block_rows: int = 8192):
-    lib = _lib.load()
     if not (isinstance(embeddings, torch.Tensor) and embeddings.is_cuda and embeddings.dim() == 2):
         raise RuntimeError("build_ii_knn: embeddings must be a 2-D ROCm tensor (there is no CPU path)")
-    if k < 1 or k > int(lib.ppgat_knn_max_k()):
-        raise NotImplementedError(f"build_ii_knn: k={k} outside [1, {int(lib.ppgat_knn_max_k())}]")
+    if k < 1 or k > _launch.knn_max_k():
+        raise NotImplementedError(f"build_ii_knn: k={k} outside [1, {_launch.knn_max_k()}]")
     e = embeddings.to(torch.float32).contiguous()
     n = e.size(0)
     dev = e.device
@@ -47,13 +46,10 @@ def build_ii_knn(embeddings: torch.Tensor, k: int = 20, min_similarity: float = 
     idx = torch.empty(n, k, dtype=torch.int32, device=dev)
     sim = torch.empty(n, k, dtype=torch.float32, device=dev)
     cnt = torch.empty(n, dtype=torch.int32, device=dev)
-    st = _lib.stream_handle(dev)
     for q0 in range(0, n, block_rows):
         q1 = min(q0 + block_rows, n)
         S = hip_ops.gemm_nn(exp[q0:q1], exp, 1, n_p)  # [q, n_p]: the similarity block, columns >= n unused
-        _lib.check(lib.ppgat_knn_topk(S.data_ptr(), n_p, q1 - q0, n, q0, k, float(min_similarity),
-                                      idx[q0:].data_ptr(), sim[q0:].data_ptr(), cnt[q0:].data_ptr(), st),
-                   "knn_topk")
+        _launch.knn_topk(S, n_p, q0, q1 - q0, n, k, min_similarity, idx, sim, cnt)
     keep = torch.arange(k, device=dev)[None, :] < cnt[:, None].to(torch.int64)
     rows = torch.arange(n, device=dev, dtype=torch.int32)[:, None].expand(n, k)[keep]
     return rows, idx[keep], sim[keep]

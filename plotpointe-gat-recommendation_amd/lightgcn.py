@@ -15,13 +15,12 @@ No CPU path: tensors live on a ROCm device and the library must be loaded.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Dict, Tuple
 
 import numpy as np
 import torch
 
-from . import _lib, hip_ops
+from . import _launch, hip_ops
 
 
 def build_adj(n_users: int, n_items: int, train_pos_idx: Dict[int, np.ndarray]) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -77,10 +76,7 @@ class LGCNGraph:
         key = (id(sched), channels)
         ws = self._ws.get(key)
         if ws is None:
-            nb = ctypes.c_size_t(0)
-            _lib.check(_lib.load().ppgat_lgcn_hop_workspace_bytes(sched.n_hub_items, channels, ctypes.byref(nb)),
-                       "lgcn_hop_workspace_bytes")
-            ws = self._ws[key] = torch.empty(int(nb.value), dtype=torch.uint8, device=self.device)
+            ws = self._ws[key] = _launch.lgcn_hop_workspace(sched.n_hub_items, channels, self.device)
         return ws
 
 
@@ -111,7 +107,7 @@ graph_cache = _GraphCache()
 
 
 def supported(channels: int) -> bool:
-    return bool(_lib.load().ppgat_lgcn_supported(int(channels)))
+    return _launch.lgcn_supported(channels)
 
 
 def hop(graph: LGCNGraph, src, acc_in=None, div: float = 1.0, want_out: bool = True, accw=None,
@@ -120,7 +116,6 @@ def hop(graph: LGCNGraph, src, acc_in=None, div: float = 1.0, want_out: bool = T
     out = s when ``want_out`` and accw = (acc_in + s) / div when ``accw`` (a tensor to write, which
     may be acc_in itself) or ``acc_in`` is given.  ``src`` / ``acc_in``: one [N, C] tensor or a
     pair of row segments (top, bottom)."""
-    lib = _lib.load()
     g = graph.g
     N, E = graph.n_nodes, graph.n_edges
     dev = graph.device
@@ -151,11 +146,7 @@ def hop(graph: LGCNGraph, src, acc_in=None, div: float = 1.0, want_out: bool = T
     idx = g.row if transpose else g.col
     val = graph.val_t if transpose else graph.val_csr
     ws = graph.workspace(sched, C) if sched.n_hub_items > 0 and supported(C) else None
-    cs = sched.cstruct()
-    _lib.check(lib.ppgat_lgcn_hop(ctypes.byref(cs), _lib.ptr(idx) if E else None, _lib.ptr(val) if E else None, N, N,
-                                  E, C, s0.data_ptr(), _lib.ptr(s1), ssplit, _lib.ptr(a0), _lib.ptr(a1), asplit,
-                                  float(div), _lib.ptr(out), _lib.ptr(accw), _lib.ptr(ws),
-                                  ws.numel() if ws is not None else 0, _lib.stream_handle(dev)), "lgcn_hop")
+    _launch.lgcn_hop(sched, idx, val, N, E, C, s0, s1, ssplit, a0, a1, asplit, div, out, accw, ws)
     return out, accw
 
 

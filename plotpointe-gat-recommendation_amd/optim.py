@@ -24,12 +24,11 @@ checks into a device flag that ``check_rows()`` reads: one sync there, none in `
 """
 from __future__ import annotations
 
-import ctypes
 import math
 
 import torch
 
-from . import _lib
+from . import _launch
 
 
 class Adam(torch.optim.Optimizer):
@@ -55,20 +54,19 @@ class Adam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        lib = _lib.load()
-        cap = int(lib.ppgat_adam_max_tensors())
+        cap = _launch.adam_max_tensors()
         for group in self.param_groups:
             b1, b2 = group["betas"]
             batch = []
             if group.get("capturable", False):
-                self._step_device(lib, cap, group)
+                self._step_device(cap, group)
                 continue
             for p in group["params"]:
                 if p.grad is None:
                     continue
                 g = p.grad
                 if g.is_sparse:
-                    self._step_rows(lib, p, g, group, b1, b2)
+                    self._step_rows(p, g, group, b1, b2)
                     continue
                 if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and g.is_contiguous()
                         and g.dtype == torch.float32):
@@ -83,13 +81,13 @@ class Adam(torch.optim.Optimizer):
                 batch.append((p, g, st["exp_avg"], st["exp_avg_sq"], group["lr"] / (1.0 - b1 ** t),
                               math.sqrt(1.0 - b2 ** t)))
                 if len(batch) == cap:
-                    self._launch(lib, batch, group, b1, b2)
+                    self._step_dense(batch, group, b1, b2)
                     batch = []
             if batch:
-                self._launch(lib, batch, group, b1, b2)
+                self._step_dense(batch, group, b1, b2)
         return loss
 
-    def _step_device(self, lib, cap, group):
+    def _step_device(self, cap, group):
         b1, b2 = group["betas"]
         ps = [p for p in group["params"] if p.grad is not None]
         if not ps:
@@ -114,19 +112,12 @@ class Adam(torch.optim.Optimizer):
         torch._foreach_add_(steps, 1.0)  # one launch, on the stream: graph replays advance every count
         for k in range(0, len(ps), cap):
             chunk = ps[k:k + cap]
-            n = len(chunk)
-            dev = chunk[0].device
-            P = (ctypes.c_void_p * n)(*[p.data_ptr() for p in chunk])
-            G = (ctypes.c_void_p * n)(*[p.grad.data_ptr() for p in chunk])
-            M = (ctypes.c_void_p * n)(*[self.state[p]["exp_avg"].data_ptr() for p in chunk])
-            V = (ctypes.c_void_p * n)(*[self.state[p]["exp_avg_sq"].data_ptr() for p in chunk])
-            NE = (ctypes.c_int64 * n)(*[p.numel() for p in chunk])
-            T = (ctypes.c_void_p * n)(*[self.state[p]["step"].data_ptr() for p in chunk])
-            _lib.check(lib.ppgat_adam_step_device(n, P, G, M, V, NE, T, float(group["lr"]), float(b1), float(b2),
-                                                  float(group["eps"]), float(group["weight_decay"]),
-                                                  _lib.stream_handle(dev)), "adam_step_device")
+            st = [self.state[p] for p in chunk]
+            _launch.adam_step_device(chunk, [p.grad for p in chunk], [s["exp_avg"] for s in st],
+                                     [s["exp_avg_sq"] for s in st], [s["step"] for s in st], group["lr"], b1, b2,
+                                     group["eps"], group["weight_decay"])
 
-    def _step_rows(self, lib, p, g, group, b1, b2):
+    def _step_rows(self, p, g, group, b1, b2):
         """The lazy step of one 2-D table on the rows its sparse gradient names (ppgat_adam_rows)."""
         if not (p.is_cuda and p.dtype == torch.float32 and p.dim() == 2 and p.is_contiguous()):
             raise RuntimeError("ppgat Adam: a sparse gradient needs a 2-D fp32 contiguous ROCm parameter")
@@ -149,11 +140,8 @@ class Adam(torch.optim.Optimizer):
         flag = self._row_flags.get(p.device)
         if flag is None:
             flag = self._row_flags[p.device] = torch.zeros(1, dtype=torch.int32, device=p.device)
-        _lib.check(lib.ppgat_adam_rows(p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
-                                       val.data_ptr(), idx.data_ptr(), idx.numel(), p.size(0), p.size(1),
-                                       group["lr"] / (1.0 - b1 ** t), math.sqrt(1.0 - b2 ** t), float(b1), float(b2),
-                                       float(group["eps"]), float(group["weight_decay"]), flag.data_ptr(),
-                                       _lib.stream_handle(p.device)), "adam_rows")
+        _launch.adam_rows(p, st["exp_avg"], st["exp_avg_sq"], val, idx, group["lr"] / (1.0 - b1 ** t),
+                          math.sqrt(1.0 - b2 ** t), b1, b2, group["eps"], group["weight_decay"], flag)
 
     def check_rows(self):
         """Read and clear the row-contract flag of every sparse step so far (one sync): raises
@@ -172,18 +160,10 @@ class Adam(torch.optim.Optimizer):
             raise RuntimeError("ppgat Adam: sparse-gradient contract violated: " + "; ".join(what))
 
     @staticmethod
-    def _launch(lib, batch, group, b1, b2):
-        n = len(batch)
+    def _step_dense(batch, group, b1, b2):
         dev = batch[0][0].device
         for p, *_ in batch:
             if p.device != dev:
                 raise RuntimeError("ppgat Adam: all parameters of a group must be on one device")
-        P = (ctypes.c_void_p * n)(*[b[0].data_ptr() for b in batch])
-        G = (ctypes.c_void_p * n)(*[b[1].data_ptr() for b in batch])
-        M = (ctypes.c_void_p * n)(*[b[2].data_ptr() for b in batch])
-        V = (ctypes.c_void_p * n)(*[b[3].data_ptr() for b in batch])
-        NE = (ctypes.c_int64 * n)(*[b[0].numel() for b in batch])
-        SS = (ctypes.c_float * n)(*[b[4] for b in batch])
-        BC = (ctypes.c_float * n)(*[b[5] for b in batch])
-        _lib.check(lib.ppgat_adam_step(n, P, G, M, V, NE, SS, BC, float(b1), float(b2), float(group["eps"]),
-                                       float(group["weight_decay"]), _lib.stream_handle(dev)), "adam_step")
+        P, G, M, V, SS, BC = (list(c) for c in zip(*batch))
+        _launch.adam_step(P, G, M, V, SS, BC, b1, b2, group["eps"], group["weight_decay"])

@@ -19,12 +19,10 @@ distribution the device draws from, q_i = w_i / total, is known exactly; ``corre
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 import torch
 
-from . import _lib
+from . import _launch
 
 
 def quantise_item_weights(item_weights, n_items: int):
@@ -76,7 +74,6 @@ class BPRSampler:
         self.weighted = item_weights is not None
         if self.weighted:  # host work first: a bad weight vector raises before anything touches a device
             self.w, cdf, self.total, log_q = quantise_item_weights(item_weights, n_items)
-        lib = _lib.load()
         dev = torch.device(device) if device is not None else (
             user_ptr.device if isinstance(user_ptr, torch.Tensor) else torch.device("cuda"))
         if dev.type != "cuda":
@@ -95,15 +92,8 @@ class BPRSampler:
         self.items = torch.empty(max(self.nnz, 1), dtype=torch.int32, device=dev)
         self.eligible = torch.empty(max(self.n_users, 1), dtype=torch.int32, device=dev)
         self.n_eligible = torch.zeros(1, dtype=torch.int64, device=dev)
-        nb = ctypes.c_size_t(0)
-        _lib.check(lib.ppgat_bpr_sampler_workspace_bytes(self.n_users, self.nnz, ctypes.byref(nb)),
-                   "bpr_sampler_workspace_bytes")
-        ws = torch.empty(max(nb.value, 1), dtype=torch.uint8, device=dev)
-        _lib.check(lib.ppgat_bpr_sampler_prepare(self.ptr.data_ptr(), items.data_ptr() if self.nnz else None,
-                                                 self.n_users, self.nnz, self.items.data_ptr(),
-                                                 self.eligible.data_ptr(), self.n_eligible.data_ptr(),
-                                                 ws.data_ptr(), nb.value, _lib.stream_handle(dev)),
-                   "bpr_sampler_prepare")
+        _launch.bpr_sampler_prepare(self.ptr, items, self.n_users, self.nnz, self.items, self.eligible,
+                                    self.n_eligible)
         self._bad = torch.zeros(1, dtype=torch.int32, device=dev)
         self.pool_tries = None
         if self.weighted:
@@ -151,31 +141,17 @@ class BPRSampler:
     def weighted_draws(self, n: int, seed: int = 42, offset: int = 0) -> torch.Tensor:
         """int64 [n]: weighted draw (seed, offset + k, 0) for k < n (ppgat_weighted_draws)."""
         self._need_weights("weighted_draws")
-        lib = _lib.load()
         out = torch.empty(int(n), dtype=torch.int64, device=self.device)
-        _lib.check(lib.ppgat_weighted_draws(self.cdf.data_ptr(), self.n_items, int(n), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                            int(offset), out.data_ptr(), _lib.stream_handle(self.device)),
-                   "weighted_draws")
+        _launch.weighted_draws(self.cdf, self.n_items, int(n), seed, int(offset), out)
         return out
 
     def sample(self, samples: int, seed: int = 42, offset: int = 0, check: bool = True):
         """-> (u, i, j) int64 [samples] on the sampler's device.  ``check`` syncs once to
         raise if no user has items or a negative could not be drawn (user holds ~all items)."""
-        lib = _lib.load()
         out = torch.empty(3, samples, dtype=torch.int64, device=self.device)
-        if self.weighted:  # u and i as below, j under the item weights
-            _lib.check(lib.ppgat_weighted_bpr_sample(self.ptr.data_ptr(), self.items.data_ptr(),
-                                                     self.eligible.data_ptr(), self.n_eligible.data_ptr(),
-                                                     self.n_items, self.cdf.data_ptr(), samples,
-                                                     int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset), out[0].data_ptr(),
-                                                     out[1].data_ptr(), out[2].data_ptr(), self._bad.data_ptr(),
-                                                     _lib.stream_handle(self.device)), "weighted_bpr_sample")
-        else:
-            _lib.check(lib.ppgat_bpr_sample(self.ptr.data_ptr(), self.items.data_ptr(), self.eligible.data_ptr(),
-                                            self.n_eligible.data_ptr(), self.n_items, samples,
-                                            int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset), out[0].data_ptr(),
-                                            out[1].data_ptr(), out[2].data_ptr(), self._bad.data_ptr(),
-                                            _lib.stream_handle(self.device)), "bpr_sample")
+        # u and i the same either way; with item weights j is drawn under them
+        _launch.bpr_sample(self.ptr, self.items, self.eligible, self.n_eligible, self.n_items, samples, seed,
+                           int(offset), out, self._bad, cdf=self.cdf if self.weighted else None)
         if check and samples > 0:
             bad = int(self._bad.item())
             if bad & 1:
@@ -198,17 +174,12 @@ class BPRSampler:
         (ppgat_weighted_eval_sample); without, ``eval_candidates`` itself."""
         if not self.weighted:
             return self.eval_candidates(users, pos, n_neg, seed, check=check)
-        lib = _lib.load()
         u = torch.as_tensor(users).to(self.device, torch.int64).contiguous()
         p = torch.as_tensor(pos).to(self.device, torch.int64).contiguous()
         if u.numel() != p.numel():
             raise ValueError("train_candidates: users and pos must have the same length")
         cands = torch.empty(u.numel(), int(n_neg) + 1, dtype=torch.int64, device=self.device)
-        _lib.check(lib.ppgat_weighted_eval_sample(self.ptr.data_ptr(), self.items.data_ptr(), u.data_ptr(),
-                                                  p.data_ptr(), u.numel(), int(n_neg), self.n_items,
-                                                  self.cdf.data_ptr(), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                                  cands.data_ptr(), self._bad.data_ptr(),
-                                                  _lib.stream_handle(self.device)), "weighted_eval_sample")
+        _launch.eval_sample(self.ptr, self.items, u, p, int(n_neg), self.n_items, seed, cands, self._bad, cdf=self.cdf)
         if check and u.numel() > 0 and int(self._bad.item()) & 2:
             raise ValueError("train_candidates: every item of positive weight is in a user's train list or is "
                              "its positive; no negative found")
@@ -260,7 +231,6 @@ class BPRSampler:
         (the last batch is partial).  (u, i) equal the reference's batches exactly; j is the first
         draw of the counter stream (seed, triple index, d) outside the user's items
         (``ppgat_bpr_sample_positives``)."""
-        lib = _lib.load()
         npp, bs, b = int(neg_per_pos), int(batch_size), int(batch)
         total = self.nnz * npp
         if npp < 1 or bs < 1 or b < 0 or b * bs >= max(total, 1):
@@ -268,11 +238,8 @@ class BPRSampler:
         t0 = b * bs
         S = min(bs, total - t0)
         out = torch.empty(3, S, dtype=torch.int64, device=self.device)
-        _lib.check(lib.ppgat_bpr_sample_positives(self.ptr.data_ptr(), self.items_orig.data_ptr(),
-                                                  self.items.data_ptr(), self.n_users, self.nnz, self.n_items, npp,
-                                                  S, int(seed) & 0xFFFFFFFFFFFFFFFF, t0, out[0].data_ptr(),
-                                                  out[1].data_ptr(), out[2].data_ptr(), self._bad.data_ptr(),
-                                                  _lib.stream_handle(self.device)), "bpr_sample_positives")
+        _launch.bpr_sample_positives(self.ptr, self.items_orig, self.items, self.n_users, self.nnz, self.n_items, npp,
+                                     S, seed, t0, out, self._bad)
         if check and int(self._bad.item()) & 2:
             raise ValueError("BPRSampler: a user holds (almost) every item; no negative found")
         return out[0], out[1], out[2]
@@ -284,16 +251,12 @@ class BPRSampler:
         """eval_sampled's candidates (train_gat_pyg.py:157-167) on the device: [B, n_neg + 1]
         int64, column 0 the held-out positive, then n_neg negatives drawn uniformly from the
         items outside the user's train list and != the positive (ppgat_eval_sample)."""
-        lib = _lib.load()
         u = torch.as_tensor(users).to(self.device, torch.int64).contiguous()
         p = torch.as_tensor(pos).to(self.device, torch.int64).contiguous()
         if u.numel() != p.numel():
             raise ValueError("eval_candidates: users and pos must have the same length")
         cands = torch.empty(u.numel(), int(n_neg) + 1, dtype=torch.int64, device=self.device)
-        _lib.check(lib.ppgat_eval_sample(self.ptr.data_ptr(), self.items.data_ptr(), u.data_ptr(), p.data_ptr(),
-                                         u.numel(), int(n_neg), self.n_items, int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                         cands.data_ptr(), self._bad.data_ptr(), _lib.stream_handle(self.device)),
-                   "eval_sample")
+        _launch.eval_sample(self.ptr, self.items, u, p, int(n_neg), self.n_items, seed, cands, self._bad)
         if check and u.numel() > 0 and int(self._bad.item()) & 2:
             raise ValueError("eval_candidates: a user holds (almost) every item; no negative found")
         return cands

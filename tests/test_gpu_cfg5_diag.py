@@ -124,7 +124,7 @@ def test_cfg5_full_diag(pkg, oracle, cuda):
     note("small-graph vs full-graph output", json.dumps(small))
     del out_s
     # train mode (attention dropout 0.1, fixed seed), the kink sides tapped, plus the hub row
-    ops = importlib.import_module("plotpointe-gat-recommendation_amd.hip_ops")
+    ops = importlib.import_module("plotpointe-gat-recommendation_amd.ops_graph")  # KINK_TAP lives there
     cm = importlib.import_module("plotpointe-gat-recommendation_amd.conv")
     hub = int(np.argmax(indeg))
     rows_t = rows + [hub]

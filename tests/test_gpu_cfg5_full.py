@@ -61,7 +61,7 @@ def test_cfg5_full_graph_layer(pkg, oracle, cuda):
 
 
 def _run(pkg, oracle, cuda, stage):
-    ops = importlib.import_module("plotpointe-gat-recommendation_amd.hip_ops")
+    ops_graph = importlib.import_module("plotpointe-gat-recommendation_amd.ops_graph")  # KINK_TAP lives there
     cm = importlib.import_module("plotpointe-gat-recommendation_amd.conv")
     H, C = 4, 256
     g = pkg.data.synthetic_scaling_graph(1.0, seed=42)
@@ -97,13 +97,13 @@ def _run(pkg, oracle, cuda, stage):
         res = []
         for rep in range(2):
             stage["now"] = f"layer forward + backward, pass {rep}"
-            ops.KINK_TAP = [] if rep == 0 else None
+            ops_graph.KINK_TAP = [] if rep == 0 else None
             try:
                 out = conv(xd, ei)
                 if rep == 0:
-                    tap = [(e, p[..., None] if p.dim() == 1 else p) for e, p in ops.KINK_TAP]
+                    tap = [(e, p[..., None] if p.dim() == 1 else p) for e, p in ops_graph.KINK_TAP]
             finally:
-                ops.KINK_TAP = None
+                ops_graph.KINK_TAP = None
             (out * Gd).sum().backward()
             torch.cuda.synchronize()
             now = (out.detach()[rows_t], xd.grad, conv.lin.weight.grad, conv.att_src.grad, conv.att_dst.grad,

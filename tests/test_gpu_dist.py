@@ -102,11 +102,11 @@ def _run(rank, world, out_dir, heads, part, size="toy", dev_index=0):
         loss_fn, to_global = D.replicated_bpr_loss, D.replicated_rows_to_global
     torch.manual_seed(123 + 1000 * rank)
     if size == "cfg4":
-        pkg.hip_ops.KINK_TAP = []  # the LeakyReLU side of every local logit (for the oracle)
+        pkg.ops_graph.KINK_TAP = []  # the LeakyReLU side of every local logit (for the oracle)
     Z = model(feats)
     if size == "cfg4":
-        torch.save([(e.cpu(), p_.cpu()) for e, p_ in pkg.hip_ops.KINK_TAP[:2]], os.path.join(out_dir, f"kinks_{rank}.pt"))
-        pkg.hip_ops.KINK_TAP = None
+        torch.save([(e.cpu(), p_.cpu()) for e, p_ in pkg.ops_graph.KINK_TAP[:2]], os.path.join(out_dir, f"kinks_{rank}.pt"))
+        pkg.ops_graph.KINK_TAP = None
     loss = loss_fn(Z, dg, comm, u, i, j, g.n_users, g.n_items)
     loss.backward()
     model.allreduce_grads()
@@ -315,14 +315,14 @@ def _run_cfg5(rank, world, out_dir):
     hg = D.build_halo_graph(torch.from_numpy(ei_np).to(dev), g.n_nodes, g.n_users, world, rank)
     own = torch.from_numpy(hg.own_node_ids())
     x_own = x[own].to(dev).requires_grad_(True)
-    pkg.hip_ops.KINK_TAP = []
+    pkg.ops_graph.KINK_TAP = []
     try:
         out = D._HaloLayerX.apply(x_own, None, conv.lin.weight, conv.att_src, conv.att_dst, conv.bias, hg, comm,
                                   pkg.hip_ops.HipStages(), conv.heads, conv.out_channels, float(conv.negative_slope),
                                   float(conv.dropout), CFG5_SEED)
-        kinks = [(e.cpu(), p_.cpu()) for e, p_ in pkg.hip_ops.KINK_TAP]
+        kinks = [(e.cpu(), p_.cpu()) for e, p_ in pkg.ops_graph.KINK_TAP]
     finally:
-        pkg.hip_ops.KINK_TAP = None
+        pkg.ops_graph.KINK_TAP = None
     (out * G[own].to(dev)).sum().backward()
     torch.cuda.synchronize()
     plans = {"n_own": hg.n_own, "n_halo_users": hg.plan_u.n_recv, "n_halo_items": hg.plan_i.n_recv,

@@ -127,26 +127,27 @@ def _check(fig, edge_grads=("dlin_edge", "datt_edge")):
 # ---------------------------------------------------------------------------------------------
 # staging
 # ---------------------------------------------------------------------------------------------
-def test_staging_tables_and_cache(hip_ops, graphs, cuda):
+def test_staging_tables_and_cache(pkg, hip_ops, graphs, cuda):
     """attr[csr_eid] and attr[csc_eid] bit for bit; the same tensor again does no work; an in-place
     edit restages; a 1-D tensor stages as [E, 1]."""
+    ops_graph = importlib.import_module(pkg.__name__ + ".ops_graph")  # the counter lives where it is counted
     g, E = graphs.by_max[256], graphs.E
     rng = np.random.default_rng(3)
     for D in (1, 3, 16):
         attr = torch.from_numpy(rng.random((E, D)).astype(np.float32)).to(cuda)
-        n0 = hip_ops.EDGE_STAGE_COUNT
+        n0 = ops_graph.EDGE_STAGE_COUNT
         a_csr, a_csc = hip_ops.stage_edge_attr(g, attr)
-        assert hip_ops.EDGE_STAGE_COUNT == n0 + 1
+        assert ops_graph.EDGE_STAGE_COUNT == n0 + 1
         assert torch.equal(a_csr, attr[g.csr_eid.long()]) and torch.equal(a_csc, attr[g.csc_eid.long()])
         b_csr, b_csc = hip_ops.stage_edge_attr(g, attr)
-        assert hip_ops.EDGE_STAGE_COUNT == n0 + 1 and b_csr is a_csr and b_csc is a_csc
+        assert ops_graph.EDGE_STAGE_COUNT == n0 + 1 and b_csr is a_csr and b_csc is a_csc
         attr[5:9].mul_(2.0)
         c_csr, c_csc = hip_ops.stage_edge_attr(g, attr)
-        assert hip_ops.EDGE_STAGE_COUNT == n0 + 2 and c_csr is not a_csr
+        assert ops_graph.EDGE_STAGE_COUNT == n0 + 2 and c_csr is not a_csr
         assert torch.equal(c_csr, attr[g.csr_eid.long()]) and torch.equal(c_csc, attr[g.csc_eid.long()])
         # an equal tensor that is another object is another entry (no keying on contents or addresses)
         hip_ops.stage_edge_attr(g, attr.clone())
-        assert hip_ops.EDGE_STAGE_COUNT == n0 + 3
+        assert ops_graph.EDGE_STAGE_COUNT == n0 + 3
     flat = torch.from_numpy(rng.random(E).astype(np.float32)).to(cuda)
     f_csr, f_csc = hip_ops.stage_edge_attr(g, flat)
     assert tuple(f_csr.shape) == (E, 1) and torch.equal(f_csr[:, 0], flat[g.csr_eid.long()])
@@ -307,7 +308,8 @@ def test_no_grad_forward_makes_no_backward_table(pkg, hip_ops, graphs, cuda, mon
     """Eval / export: the forward asks for the CSR term table only."""
     asked = []
     real = hip_ops.edge_terms
-    monkeypatch.setattr(hip_ops, "edge_terms", lambda g, s, v, h, want_csc: asked.append(want_csc) or
+    ops_gat = importlib.import_module(pkg.__name__ + ".ops_gat")  # where GATLayer.forward looks edge_terms up
+    monkeypatch.setattr(ops_gat, "edge_terms", lambda g, s, v, h, want_csc: asked.append(want_csc) or
                         real(g, s, v, h, want_csc))
     conv = pkg.GATConv(128, 64, heads=1, edge_dim=1, concat=False, add_self_loops=False).to(cuda).eval()
     x = torch.from_numpy(np.array(_inputs(1, 64, 1)["x"])).to(cuda)

@@ -48,6 +48,10 @@ def _ops():
     return importlib.import_module("plotpointe-gat-recommendation_amd.hip_ops")
 
 
+def _graph():  # where KINK_TAP lives (module state is not re-exported by hip_ops)
+    return importlib.import_module("plotpointe-gat-recommendation_amd.ops_graph")
+
+
 @pytest.fixture(scope="module")
 def cfg2(pkg):
     d = pkg.data
@@ -73,12 +77,12 @@ def _train_step_check(pkg, oracle, cuda, g, ei_np, feats_np, triples, name):
     tu, ti, tj = (torch.from_numpy(a) for a in triples)
     # device step: the two layers' dropout seeds are drawn from torch's CPU generator
     torch.manual_seed(777)
-    _ops().KINK_TAP = []  # the LeakyReLU side of every logit in this forward (for the oracle)
+    _graph().KINK_TAP = []  # the LeakyReLU side of every logit in this forward (for the oracle)
     try:
         Z = m(feats.to(cuda), ei.to(cuda))
-        sides = kink_sides(_ops().KINK_TAP, ei_np.shape[1], 1, 2)
+        sides = kink_sides(_graph().KINK_TAP, ei_np.shape[1], 1, 2)
     finally:
-        _ops().KINK_TAP = None
+        _graph().KINK_TAP = None
     loss = pkg.bpr_loss(Z, g.n_users, tu.to(cuda), ti.to(cuda), tj.to(cuda))
     loss.backward()
     torch.cuda.synchronize()
@@ -205,12 +209,12 @@ def test_cfg5_share_layer_full_gradients(pkg, oracle, cuda):
         ei = torch.from_numpy(ei_np).to(cuda)
         xd = x.to(cuda).requires_grad_(True)
         Gd = Gup.to(cuda)
-        _ops().KINK_TAP = []
+        _graph().KINK_TAP = []
         try:
             out = conv(xd, ei)
-            sides = kink_sides(_ops().KINK_TAP, E, H, 1)
+            sides = kink_sides(_graph().KINK_TAP, E, H, 1)
         finally:
-            _ops().KINK_TAP = None
+            _graph().KINK_TAP = None
         (out * Gd).sum().backward()
         torch.cuda.synchronize()
         res1 = (out.detach().clone(), xd.grad.clone(), conv.lin.weight.grad.clone(), conv.att_src.grad.clone(),

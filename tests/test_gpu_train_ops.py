@@ -299,4 +299,4 @@ def test_side_stream_weight_grads_bitwise(pkg, cuda, monkeypatch):
     for k in ref:
         assert torch.equal(got[k], ref[k]), k
         assert torch.equal(acc[k], acc_ref[k]), k
-    assert pkg.hip_ops._PENDING_JOINS == []
+    assert pkg.ops_gat._PENDING_JOINS == []

@@ -23,6 +23,14 @@ def _ops():
     return importlib.import_module("plotpointe-gat-recommendation_amd.hip_ops")
 
 
+def _ops_gemm():  # the module that holds _CONST_BOUNDS
+    return importlib.import_module("plotpointe-gat-recommendation_amd.ops_gemm")
+
+
+def _ops_xgat():  # the module whose code looks up _xgat_weight_grads
+    return importlib.import_module("plotpointe-gat-recommendation_amd.ops_xgat")
+
+
 @pytest.mark.parametrize("M,K,N,layout", [(1000, 256, 256, 1), (3001, 1024, 256, 0), (777, 256, 1024, 0),
                                           (130, 32, 128, 1), (5000, 256, 384, 0)])
 def test_gemm_nn_vs_fp64(cuda, M, K, N, layout):
@@ -197,7 +205,7 @@ def test_weight_grad_bound_ignores_rows_without_out_edges(pkg, oracle, cuda):
         return real(*a, **k)
     import pytest as _pt
     mp = _pt.MonkeyPatch()
-    mp.setattr(ops, "_xgat_weight_grads", spy)
+    mp.setattr(_ops_xgat(), "_xgat_weight_grads", spy)
     try:
         out = conv(x, torch.from_numpy(ei).to(cuda))
         (out * G64.float().to(cuda)).sum().backward()
@@ -239,7 +247,7 @@ def test_linear_constant_input_bound_cached(pkg, cuda):
         bd = b.float().to(cuda).requires_grad_(True)
         (ops.linear(xd, Wd, bd) * G.float().to(cuda)).sum().backward()
         assert rel(Wd.grad, ref) <= 1e-5
-        e = ops._CONST_BOUNDS.get(id(xd))
+        e = _ops_gemm()._CONST_BOUNDS.get(id(xd))
         assert e is not None and e[0]() is xd and e[1][0] == xd._version and e[1][1] == xd.data_ptr()
         if it == 1:
             xd.mul_(2.0)                          # a new version: the bound is recomputed

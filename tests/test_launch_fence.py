@@ -1,7 +1,10 @@
 """The launch fence of the Python package (no GPU, no build: reads the files).
 
-The GAT layers' kernels are launched from _launch.py alone: row offsets become addresses in
-_lib.row_ptr, and dist.py -- exchanges, phases, streams -- never touches the C ABI itself.
+Every kernel is launched from _launch.py alone: no other module imports ctypes or names an ABI
+entry (_lib.py binds the library and calls the few entries it needs for itself), row offsets
+become addresses in _lib.row_ptr, and dist.py -- exchanges, phases, streams -- never touches the
+C ABI itself.  hip_ops is the import surface of the ops_* modules: every name it had before the
+split still resolves there, except the module state that a facade would serve stale.
 """
 from __future__ import annotations
 
@@ -11,26 +14,100 @@ from importlib import import_module
 from pathlib import Path
 
 PKG = Path(__file__).resolve().parents[1] / "plotpointe-gat-recommendation_amd"
+ABI_MODULES = ("_lib.py", "_launch.py")
+
+# declared in _lib.SIGNATURES, called by no Python of the package
+DECLARED_UNUSED = {"ppgat_version", "ppgat_stream_copy", "ppgat_fusion_fwd", "ppgat_gemm_nn", "ppgat_xgat_fwd",
+                   "ppgat_xgat_bwd_edges_gd", "ppgat_shs_supported", "ppgat_full_rank_supported",
+                   "ppgat_full_topk_supported", "ppgat_full_topk_max_k", "ppgat_neighbor_max_fanout",
+                   "ppgat_subgraph_max_hops"}
+
+# The names hip_ops.py exposed when it was one file (its 120 non-dunder names, listed from that
+# file): the functions, classes and constants, which still resolve on hip_ops ...
+HIP_OPS_SURFACE = (
+    "BprPrepared", "CSRGraph", "EDGE_MAX_DIM", "GATAggregate", "GATLayer", "GATLayerX", "GATv2Aggregate", "HipStages",
+    "LOSS_KINDS", "MAX_EDGES_PER_ITEM", "Schedule", "XPhase", "XViews", "_BPRLoss", "_BadIndex", "_EmbeddingRows",
+    "_GraphCache", "_JoinRows", "_Linear", "_ORDERS", "_SharedSoftmaxLoss", "_SoftmaxLoss", "_aligned_rows",
+    "_async_wgrad_enabled", "_attention_out", "_bwd_dst_sum", "_bwd_edges_dst", "_bwd_edges_src", "_check_correction",
+    "_check_dev", "_check_rows", "_check_state", "_const_colmax", "_csr2csc", "_fused_dxw_enabled", "_fwd_outputs",
+    "_fwd_rows", "_gatv2_require_shape", "_grad_free", "_join_side_streams", "_pad_cols4", "_producer_fusion_enabled",
+    "_producer_of", "_require", "_run_on_side", "_side_stream", "_tap_kinks", "_track_correction",
+    "_xgat_backward_deferred_d", "_xgat_bytes", "_xgat_dst_sum", "_xgat_gather_mode", "_xgat_keep_agg",
+    "_xgat_weight_grads", "_xgat_weight_grads_from_G", "att_proj", "attention_topk", "attention_weights", "bpr_loss",
+    "bpr_loss_mapped", "bpr_prepare", "check_bpr_indices", "check_edge_attr", "colmax_abs", "colsum", "csr_build",
+    "debug_validate_graph", "edge_terms", "embedding_rows", "gat_aggregate", "gat_bwd", "gat_fwd", "gat_layer",
+    "gat_layer_attention", "gat_layer_x", "gatv2_aggregate", "gatv2_attention_weights", "gatv2_layer_attention",
+    "gatv2_supported", "gemm_nn", "gemm_nn_supported", "gemm_tn", "gemm_tn_big", "gemm_tn_big_supported",
+    "graph_cache", "join_rows", "linear", "mm_nn", "node_scores", "project", "project_supported", "rank_update_",
+    "rows_adjacent", "schedule_build", "seed_buffer", "shared_softmax_loss", "shared_softmax_loss_corrected",
+    "softmax_loss", "stage_edge_attr", "weight_grads", "xgat_att_proj", "xgat_backward", "xgat_forward",
+    "xgat_scores_rows", "xgat_supported")
+# ... the module state, which lives only where it is rebound or counted (name -> module) ...
+HIP_OPS_STATE = {"KINK_TAP": "ops_graph", "EDGE_STAGE_COUNT": "ops_graph", "_PENDING_JOINS": "ops_gat",
+                 "_SIDE_STREAMS": "ops_gat", "_CONST_BOUNDS": "ops_gemm"}
+# ... and what the file imported for its own use (no part of the surface)
+HIP_OPS_IMPORTS = ("Callable", "Optional", "annotations", "dataclass", "ctypes", "os", "weakref", "torch", "_launch",
+                   "_lib")
+
+
+def _imports(path: Path) -> set:
+    tree = ast.parse(path.read_text())
+    found = {a.name.split(".")[0] for n in ast.walk(tree) if isinstance(n, ast.Import) for a in n.names}
+    return found | {n.module.split(".")[0] for n in ast.walk(tree)
+                    if isinstance(n, ast.ImportFrom) and n.level == 0 and n.module}
 
 
 def test_dist_does_not_touch_the_abi():
-    tree = ast.parse((PKG / "dist.py").read_text())
-    imported = {a.name.split(".")[0] for n in ast.walk(tree) if isinstance(n, ast.Import) for a in n.names}
-    imported |= {n.module for n in ast.walk(tree) if isinstance(n, ast.ImportFrom) and n.level == 0}
-    assert "ctypes" not in imported
+    assert "ctypes" not in _imports(PKG / "dist.py")
     assert "lib.ppgat_" not in (PKG / "dist.py").read_text()
+
+
+def test_only_the_launch_layer_touches_the_abi():
+    files = sorted(p for p in PKG.glob("*.py") if p.name not in ABI_MODULES)
+    assert len(files) >= 20 and PKG / "dist.py" in files, files
+    found = [(p.name, "ctypes") for p in files if "ctypes" in _imports(p)]
+    found += [(p.name, m) for p in files for m in re.findall(r"\.ppgat_\w+", p.read_text())]
+    assert not found, found
 
 
 def test_pointer_arithmetic_lives_in_the_launch_layer():
     files = sorted(PKG.glob("*.py"))
     assert len(files) >= 15, files
-    found = [(p.name, n) for p in files if p.name not in ("_lib.py", "_launch.py")
+    found = [(p.name, n) for p in files if p.name not in ABI_MODULES
              for n, line in enumerate(p.read_text().splitlines(), 1) if re.search(r"data_ptr\(\)\s*\+", line)]
     assert not found, found
 
 
 def test_launch_layer_calls_declared_entries_only():
-    sigs = import_module("plotpointe-gat-recommendation_amd._lib").SIGNATURES
+    sigs = set(import_module("plotpointe-gat-recommendation_amd._lib").SIGNATURES)
     called = set(re.findall(r"\.(ppgat_\w+)\b", (PKG / "_launch.py").read_text()))
-    assert len(called) >= 25, called  # the entries and their workspace queries were found
-    assert called <= set(sigs), called - set(sigs)
+    assert len(called) >= 131, called  # the entries and their workspace queries were found
+    assert called <= sigs, called - sigs
+    own = set(re.findall(r"\.(ppgat_\w+)\b", (PKG / "_lib.py").read_text()))
+    assert own <= sigs, own - sigs
+    # every declared entry has a caller, or is listed as having none
+    assert DECLARED_UNUSED <= sigs and not DECLARED_UNUSED & (called | own)
+    assert sigs - called - own == DECLARED_UNUSED, (sigs - called - own) ^ DECLARED_UNUSED
+
+
+def test_hip_ops_keeps_its_surface_and_serves_no_state():
+    assert len(HIP_OPS_SURFACE) + len(HIP_OPS_STATE) + len(HIP_OPS_IMPORTS) == 120
+    assert len(set(HIP_OPS_SURFACE)) == len(HIP_OPS_SURFACE) and not set(HIP_OPS_SURFACE) & set(HIP_OPS_STATE)
+    hip_ops = import_module("plotpointe-gat-recommendation_amd.hip_ops")
+    missing = [n for n in HIP_OPS_SURFACE if not hasattr(hip_ops, n)]
+    assert not missing, missing
+    for name, home in HIP_OPS_STATE.items():
+        assert not hasattr(hip_ops, name), name  # AttributeError there, not a stale copy
+        assert hasattr(import_module("plotpointe-gat-recommendation_amd." + home), name), (home, name)
+    tree = ast.parse((PKG / "hip_ops.py").read_text())
+    assert not [n for n in ast.walk(tree) if isinstance(n, ast.ImportFrom) and any(a.name == "*" for a in n.names)]
+
+
+def test_tests_and_tools_set_nothing_on_hip_ops():
+    root = PKG.parent
+    files = sorted(root.glob("tests/*.py")) + sorted(root.glob("tools/*.py"))
+    files = [p for p in files if p != Path(__file__).resolve()]
+    assert len(files) >= 40, len(files)
+    pat = re.compile(r"\bhip_ops\.\w+\s*=[^=]|setattr\(\s*(?:\w+\.)?hip_ops\b")
+    found = [(p.name, n) for p in files for n, line in enumerate(p.read_text().splitlines(), 1) if pat.search(line)]
+    assert not found, found

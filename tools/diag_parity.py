@@ -171,7 +171,7 @@ def cfg4b():
     it = iter(seeds)
     cm._dropout_seed = lambda: next(it)
     cap = []
-    orig = ops._bwd_edges_dst
+    ops_gat = importlib.import_module("plotpointe-gat-recommendation_amd.ops_gat")  # GATLayer.backward looks it up there
 
     def spy(gr, h, s_src, nstate, grad_out, D, S, heads, channels, mode, slope, p, seed, seed_buf=None):
         dzb = torch.empty(max(gr.n_edges, 1) * heads, dtype=torch.float32, device=h.device)
@@ -182,7 +182,7 @@ def cfg4b():
                         g=grad_out.detach().clone(), D=D.detach().clone(), S=S.detach().clone(), dz=dzb.clone(),
                         csc_eid=gr.csc_eid.detach().long().clone(), row=gr.row.detach().long().clone(),
                         seed=int(seed_buf.item()) if seed_buf is not None else None))
-    ops._bwd_edges_dst = spy
+    ops_gat._bwd_edges_dst = spy
     Z = full(feats.to(cuda), ei.to(cuda))
     pkg.bpr_loss(Z, g.n_users, u.to(cuda), i.to(cuda), j.to(cuda)).backward()
     torch.cuda.synchronize()

@@ -29,7 +29,6 @@ def main():
     ap.add_argument("--steps", type=int, default=2)
     args = ap.parse_args()
     pkg = importlib.import_module("plotpointe-gat-recommendation_amd")
-    O = pkg.hip_ops
     data = pkg.data
     dev = torch.device("cuda", 0)
     log = []
@@ -49,8 +48,11 @@ def main():
             return r
         setattr(mod, name, w)
 
+    # on the modules whose code looks the names up (hip_ops only re-exports them)
     for n in ("xgat_forward", "xgat_backward", "_xgat_weight_grads", "gemm_tn_big", "colmax_abs"):
-        wrap(O, n)
+        wrap(pkg.ops_xgat, n)
+    for n in ("gemm_tn_big", "colmax_abs"):
+        wrap(pkg.ops_gemm, n)
     g = data.synthetic_scaling_graph(args.scale, seed=42)
     feats_np = data.synthetic_item_features(g.n_items, 256, seed=42)
     ei_np = g.edge_index_numpy()
